@@ -10,6 +10,14 @@ each rank owns a 2048 x 2048 x 160 J strip of a 2048 x (2048*N) x 160 global dom
 scaling) and every step exchanges the 2-row J halo of ``in_field`` over RCCL while the interior
 computes.
 
+A plain run (``--gpus 1 --steps K --warmup W``) does what the headline needs and nothing else:
+it sets the fields up (placement tuned, as below), warms up, times the K steps, writes the
+outputs of the last timed step if ``--dump-outputs DIR`` is given (``DIR/<field>.npy``, every
+field the stencil writes; a fixed seeded sample of the cells where a field is larger than its
+share of 48 MB) and prints the result line. Everything else described below -- the untuned first
+allocation's timing, ``sustained``, ``full_call``, ``extra_configs``, ``cpu_baseline``, ``box``,
+the N>1 plain-launch A/B and C5 leg -- is measured only with ``--full``.
+
 One step = one stencil application over the whole (local) domain, inputs resident in HBM.
 Timing: W untimed warmups, then K steps bracketed by barrier + synchronize; max over ranks.
 ``roofline`` = algorithmic bytes (24 B/cell: in + coeff read, out written)
@@ -630,12 +638,13 @@ class Workload:
         """Re-home the fields this stencil writes to the fastest of ``candidates + 1`` buffer sets
         through the drop-in call, ``StencilObject.tune_placement`` (in place: the argument tensors
         stay the same objects; DESIGN.md §5 "HBM placement"): done once, before any timed step, as
-        a long-running simulation would after allocating its fields. The first allocation's time is
-        measured first exactly as the headline is (K steps, HIP events), so the line carries the
-        untuned figure as well."""
-        steps, warm = (args.steps, args.warmup) if self.cfg == args.config else (args.extra_steps, 3)
-        el, km = time_workload(self, steps, warm, self.dev, None, step=self.plain_step)
-        self.untuned = {"ms_per_step": el / steps * 1e3, "kernel_ms": km}
+        a long-running simulation would after allocating its fields. With ``--full`` the first
+        allocation's time is measured first exactly as the headline is (K steps, HIP events), so
+        the line carries the untuned figure as well."""
+        if getattr(args, "full", False):
+            steps, warm = (args.steps, args.warmup) if self.cfg == args.config else (args.extra_steps, 3)
+            el, km = time_workload(self, steps, warm, self.dev, None, step=self.plain_step)
+            self.untuned = {"ms_per_step": el / steps * 1e3, "kernel_ms": km}
         try:
             self.placement = self.stencil.tune_placement(*self.args, **self.params, origin=self.origin,
                                                          scope=placement_scope(self.cfg, args),
@@ -708,6 +717,46 @@ def time_workload(wl, steps, warmup, dev, dist=None, events=True, step=None):
     elapsed = time.perf_counter() - t0
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in evs])) if evs is not None else None
     return elapsed, kernel_ms
+
+
+DUMP_BUDGET_BYTES = 48_000_000  # all files of one --dump-outputs directory together
+DUMP_SEED = 20240519
+
+
+def dump_sample_index(shape, count):
+    """The fixed sample of a field too large to dump whole: ``count`` cells of ``shape`` drawn
+    (with replacement) by a seeded generator, in ascending C order of (i, j, k); the same for
+    every run and build, so two dumps compare cell for cell."""
+    flat = np.sort(np.random.default_rng(DUMP_SEED).integers(0, int(np.prod(shape)), size=count))
+    return np.unravel_index(flat, shape)
+
+
+def dump_outputs(wl, dirpath) -> dict:
+    """``--dump-outputs``: what the last timed step left in every field the stencil writes (the
+    arrays its caller holds after the call), as ``<dirpath>/<field>.npy`` in the field's own
+    precision. A field within its share of DUMP_BUDGET_BYTES is written whole, in its (i, j, k)
+    shape; of a larger one the 1-D array of the cells ``dump_sample_index`` names."""
+    import torch
+
+    from gt4py_amd.storage.placement import written_fields
+
+    written = set(written_fields(wl.stencil))
+    fields = [(n, t) for n, t in zip(wl.stencil.field_info, wl.args) if n in written]
+    os.makedirs(dirpath, exist_ok=True)
+    if wl.dev.type == "cuda":
+        torch.cuda.synchronize()
+    done = {}
+    for name, t in fields:
+        share = DUMP_BUDGET_BYTES // len(fields)
+        if t.numel() * t.element_size() <= share:
+            arr = np.ascontiguousarray(t.cpu().numpy())
+        else:
+            idx = dump_sample_index(tuple(t.shape), share // t.element_size())
+            arr = t[tuple(torch.from_numpy(i).to(t.device) for i in idx)].cpu().numpy()
+        assert arr.dtype in (np.float32, np.float64), arr.dtype
+        np.save(os.path.join(dirpath, f"{name}.npy"), arr)
+        done[name] = arr.shape
+    return done
 
 
 def traffic_for(cfg, key):
@@ -919,11 +968,18 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", default="hdiff", choices=sorted(CONFIGS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="N=1: skip the extra_configs timings")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline: the untuned first allocation, sustained, "
+                         "full_call, extra_configs, cpu_baseline, box state, the N>1 plain-launch A/B and C5 leg "
+                         "(a plain run sets up, warms up, times --steps steps and prints the line)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write every field the stencil writes, as the last timed step "
+                         "left it, to DIR/<field>.npy (a fixed seeded sample of the cells of a large field)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the cpu_baseline legs")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra_configs timings")
     ap.add_argument("--extra-steps", type=int, default=20)
     ap.add_argument("--sustain", type=float, default=3.0,
-                    help="N=1: after the timed K steps, run the step for about this many seconds more and report "
+                    help="--full, N=1: after the timed K steps, run the step for about this many seconds more and report "
                          "the steady-state ms/step as `sustained` (0 = off)")
     ap.add_argument("--jchunk", type=int, default=None)
     ap.add_argument("--placement-candidates", type=int, default=5,
@@ -1016,13 +1072,15 @@ def main():
         phase.finish()
 
     box = None
-    if not args.dry_run:
+    if args.full and not args.dry_run:
         card, ident = box_identity(torch.cuda.current_device())
         box = {"identity": ident, "before": card_snapshot(card), "pid": os.getpid(),
                "process_uptime_s": round(time.time() - _START, 2)}
     wl = Workload(args.config, args, rank, world, dev, backend, dry_run=args.dry_run)
     elapsed, kernel_ms = time_workload(wl, args.steps, args.warmup, dev, dist)
     elapsed_rank = elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
     if dist is not None:
         tdev = dev if str(dist.get_backend()).lower() == "nccl" else "cpu"
         t = torch.tensor([elapsed, kernel_ms or 0.0], device=tdev, dtype=torch.float64)
@@ -1030,14 +1088,15 @@ def main():
         elapsed, kernel_ms = float(t[0]), (float(t[1]) if kernel_ms is not None else None)
     dist_rec = None
     if dist is not None and world > 1:
-        # the same ranks, the same buffers: one plain launch over the whole local tile with no
-        # exchange, so the line says what the exchange costs per rank (max over ranks)
-        el_p, km_p = time_workload(wl, args.steps, args.warmup, dev, dist, step=wl.plain_step)
-        el_h2, _ = time_workload(wl, args.steps, args.warmup, dev, dist)  # halo path again, interleaved
-        el_hb = min(elapsed_rank, el_h2)
-        tdev = dev if str(dist.get_backend()).lower() == "nccl" else "cpu"
-        mine = torch.tensor([el_p, km_p or 0.0, el_hb / el_p - 1.0], device=tdev, dtype=torch.float64)
-        dist.all_reduce(mine, op=dist.ReduceOp.MAX)
+        mine = km_p = None
+        if args.full:
+            # the same ranks, the same buffers: one plain launch over the whole local tile with no
+            # exchange, so the line says what the exchange costs per rank (max over ranks)
+            el_p, km_p = time_workload(wl, args.steps, args.warmup, dev, dist, step=wl.plain_step)
+            el_h2, _ = time_workload(wl, args.steps, args.warmup, dev, dist)  # halo path again, interleaved
+            el_hb = min(elapsed_rank, el_h2)
+            mine = torch.tensor([el_p, km_p or 0.0, el_hb / el_p - 1.0], device=tdev, dtype=torch.float64)
+            dist.all_reduce(mine, op=dist.ReduceOp.MAX)
         ranks = [None] * world
         me = {"rank": rank, "local_rank": local_rank, "host": os.uname().nodename}
         if dev.type == "cuda":
@@ -1055,13 +1114,16 @@ def main():
             "rccl_version": rccl,
             "ranks": ranks,
             "step_ms": round(kernel_ms, 4) if kernel_ms is not None else None,
-            "plain_ms_per_step": round(float(mine[0]) / args.steps * 1e3, 4),
-            "plain_kernel_ms": round(float(mine[1]), 4) if km_p is not None else None,
-            "exchange_overhead": round(float(mine[2]), 4),
             "halo_schedule": wl.halo.schedule() if hasattr(getattr(wl, "halo", None), "schedule") else None,
-            "note": "plain = one launch over the whole local tile on the same buffers, no exchange; "
-                    "exchange_overhead = halo-path time / plain time - 1 per rank, max over ranks",
         }
+        if mine is not None:
+            dist_rec.update({
+                "plain_ms_per_step": round(float(mine[0]) / args.steps * 1e3, 4),
+                "plain_kernel_ms": round(float(mine[1]), 4) if km_p is not None else None,
+                "exchange_overhead": round(float(mine[2]), 4),
+                "note": "plain = one launch over the whole local tile on the same buffers, no exchange; "
+                        "exchange_overhead = halo-path time / plain time - 1 per rank, max over ranks",
+            })
     halo_ab = None
     if args.halo_selfcomm and world == 1:
         # A/B on the same buffers in the same process: whole-domain launch without exchange,
@@ -1159,7 +1221,7 @@ def main():
             "all_payloads_ok": all(r["payload_ok"] for r in probe)}
     if halo_ab is not None:
         result["halo_ab"] = halo_ab
-    if world == 1 and not args.dry_run and not args.halo_selfcomm and args.sustain > 0:
+    if args.full and world == 1 and not args.dry_run and not args.halo_selfcomm and args.sustain > 0:
         # steady state over seconds rather than tens of milliseconds (clocks, HBM refresh, the
         # driver's utilisation sampler); the headline `value` stays the K-step measurement
         n_s = max(args.steps, int(args.sustain / max(elapsed / args.steps, 1e-6)))
@@ -1168,7 +1230,7 @@ def main():
         result["sustained"] = {"steps": n_s, "seconds": round(el_s, 2), "ms_per_step": round(ms_s, 4),
                                "Mcells_s": round(cells_per_step / (ms_s * 1e-3) / 1e6, 1),
                                "frac": round(cells_per_step * wl.bpc / (ms_s * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)}
-    if world == 1 and not args.dry_run and not args.halo_selfcomm:
+    if args.full and world == 1 and not args.dry_run and not args.halo_selfcomm:
         # full-call time: validate_args=True and a synchronize after every call,
         # i.e. host validation + launch + kernel + sync, as a plain reference-style call loop
         el_v, _ = time_workload(wl, args.steps, 1, dev, None, events=False, step=wl.validated_step)
@@ -1198,10 +1260,10 @@ def main():
         result["dry_run"] = True
         result["data"] = "synthetic; DRY RUN on CPU (numpy backend, gloo): not a measurement"
     del wl
-    if world > 1 and not args.no_extra and args.config != C5_CONFIG:
+    if args.full and world > 1 and not args.no_extra and args.config != C5_CONFIG:
         # BASELINE configs[4] (C5) at N>1: the f32 tile sharded the same way, in the same ranks
         result["extra_configs"] = {C5_CONFIG: sharded_leg(C5_CONFIG, args, rank, world, dev, backend, dist)}
-    if world == 1 and not args.dry_run and not args.no_extra and not args.halo_selfcomm:
+    if args.full and world == 1 and not args.dry_run and not args.no_extra and not args.halo_selfcomm:
         # the other BASELINE configs, timed in the same process after the headline (C2, C4, the C5
         # per-GPU tile, copy, vadv): per-launch kernel time from HIP events, fraction of 8 TB/s
         extra = {}
@@ -1238,11 +1300,12 @@ def main():
             torch.cuda.synchronize()
             torch.cuda.empty_cache()
         result["extra_configs"] = extra
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.dry_run:
         cb = cpu_baseline(args.config)
         if cb:
             result["cpu_baseline"] = cb
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extra and not args.halo_selfcomm:
+    if (args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.no_extra
+            and not args.halo_selfcomm):
         # BASELINE configs[1] reads "1xMI355X vs gt:cpu_ifirst" (C2) and C4 is the hot path's
         # K sweep: the same C restatement, thread policy and input distributions beside their GPU
         # figures (the dry run rehearses the plumbing on a small domain)

@@ -43,6 +43,8 @@ if [ "${ROCTX:-0}" = 1 ]; then
   find gpurun_out/roctx -name "*marker*"
 fi
 if [ "${BENCH:-0}" = 1 ]; then
-  timeout -k 10 600 python3 bench.py > gpurun_out/bench.json 2> gpurun_out/bench.err || { tail -20 gpurun_out/bench.err; exit 1; }
-  cat gpurun_out/bench.json
+  B=${BENCH_OUT:-bench_out}
+  mkdir -p $B
+  timeout -k 10 600 python3 bench.py --full > $B/bench.json 2> $B/bench.err || { tail -20 $B/bench.err; exit 1; }
+  cat $B/bench.json
 fi

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Split a rocprofv3 --kernel-trace of ``bench.py`` by code object.
+"""Split a rocprofv3 --kernel-trace of ``bench.py --full`` by code object.
 
 ``--stats`` aggregates dispatches by kernel NAME, and every gt:mi355x library names its kernel
 ``k0_plane_v2`` / ``k0_column`` / ...: one profiled bench run (headline + extra configs) mixes the

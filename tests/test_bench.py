@@ -27,7 +27,7 @@ def _run(args, env_extra=None, timeout=240):
 def test_bench_launcher_dry_run(gpus, decomp):
     """The driver's 1/2/4/8-rank command lines, rehearsed on the CPU (gloo, numpy backend, a
     64x32x8 tile per rank): one JSON line with the whole N-rank record, C5 leg included."""
-    res = _run(["--dry-run", "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--decomp", decomp],
+    res = _run(["--dry-run", "--full", "--gpus", str(gpus), "--steps", "2", "--warmup", "1", "--decomp", decomp],
                timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -86,6 +86,56 @@ def test_bench_launcher_dry_run(gpus, decomp):
         assert key in rec
 
 
+MOVED_BEHIND_FULL = ("sustained", "full_call", "extra_configs", "cpu_baseline", "box")
+
+
+def test_bench_plain_dry_run_is_lean_and_dumps_outputs(tmp_path):
+    """A plain run carries the headline fields and none of the legs behind ``--full``;
+    ``--dump-outputs`` writes the written field of the last timed step, and the same arguments
+    give the same array again. The dry run's tile is small, so the field is dumped whole."""
+    import numpy as np
+
+    recs, outs = [], []
+    for d in ("a", "b"):
+        res = _run(["--dry-run", "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / d)])
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout
+        recs.append(json.loads(lines[0]))
+        assert sorted(os.listdir(tmp_path / d)) == ["out_field.npy"]
+        outs.append(np.load(tmp_path / d / "out_field.npy"))
+    rec = recs[0]
+    assert rec["steps"] == 3 and rec["warmup"] == 1 and rec["ms_per_step"] > 0
+    assert rec["unit"] == "Mcells/s" and rec["higher_is_better"] is True and rec["dtype"] == "f64"
+    # value and ms_per_step describe the same K steps: cells of one step / ms_per_step (the line
+    # rounds value to 0.01 and ms_per_step to 1e-4)
+    assert rec["value"] == pytest.approx(64 * 32 * 8 / (rec["ms_per_step"] * 1e-3) / 1e6, rel=2e-3, abs=0.006)
+    for key in MOVED_BEHIND_FULL:
+        assert key not in rec, key
+    assert "kernel_ms_untuned" not in rec["roofline"]
+    assert outs[0].dtype == np.float64 and outs[0].shape == (64, 32, 8)
+    assert np.isfinite(outs[0]).all() and np.abs(outs[0]).max() > 0
+    assert np.array_equal(outs[0], outs[1])
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget():
+    """A field larger than its share of the dump budget is sampled at cells that depend on the
+    shape alone (seeded), in range and in ascending order; the flagship's dump stays under 64 MB."""
+    import numpy as np
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    shape = (37, 19, 11)
+    i, j, k = bench.dump_sample_index(shape, 1000)
+    i2, j2, k2 = bench.dump_sample_index(shape, 1000)
+    assert all(np.array_equal(a, b) for a, b in ((i, i2), (j, j2), (k, k2)))
+    assert len(i) == 1000 and i.max() < 37 and j.max() < 19 and k.max() < 11 and min(i.min(), j.min(), k.min()) >= 0
+    flat = np.ravel_multi_index((i, j, k), shape)
+    assert (np.diff(flat) >= 0).all() and len(np.unique(flat)) > 900
+    assert bench.DUMP_BUDGET_BYTES + 4096 <= 64 * 1000 * 1000
+
+
 def test_rank_setup_timeout_names_the_phase():
     """A rank that cannot finish process-group set-up exits non-zero with its last phase (here:
     rank 1 of a 2-rank rendezvous never starts, so rank 0 waits in init_process_group)."""
@@ -114,7 +164,7 @@ def test_bench_gpu_line_with_placement_tuning():
     """The real N=1 line on the GPU (small config): one JSON line, roofline within [0, 1], and the
     written field placed by measurement with every buffer set's time recorded (set 0 = the first
     allocation, the untuned time)."""
-    res = _run(["--config", "lap5", "--steps", "5", "--warmup", "2", "--no-extra", "--no-cpu-baseline",
+    res = _run(["--full", "--config", "lap5", "--steps", "5", "--warmup", "2", "--no-extra", "--no-cpu-baseline",
                 "--sustain", "0", "--placement-candidates", "2"], timeout=600)
     assert res.returncode == 0, res.stderr[-3000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
@@ -129,6 +179,34 @@ def test_bench_gpu_line_with_placement_tuning():
     assert rec["full_call"]["overhead_vs"] == "kernel_ms"
     r = rec["roofline"]
     assert 0.0 < r["frac_untuned"] <= 1.0 and r["kernel_ms_untuned"] > 0
+
+
+@pytest.mark.gpu
+def test_bench_gpu_plain_line_and_dumped_outputs(tmp_path):
+    """The plain N=1 run on the GPU (lap5, 1024x1024x80 f64: 671 MB, so the dump is the seeded
+    sample): headline fields only, and the dumped cells of ``out_field`` are the 5-point Laplacian
+    of inputs in U(-10, 10) -- finite, within the stencil's bound 4*10 + 4*10, not all zero --
+    and identical in a second run with the same arguments."""
+    import numpy as np
+
+    outs = []
+    for d in ("a", "b"):
+        res = _run(["--config", "lap5", "--steps", "4", "--warmup", "1", "--placement-candidates", "1",
+                    "--dump-outputs", str(tmp_path / d)], timeout=600)
+        assert res.returncode == 0, res.stderr[-3000:]
+        lines = [ln for ln in res.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, res.stdout
+        rec = json.loads(lines[0])
+        assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["dtype"] == "f64" and rec["unit"] == "Mcells/s"
+        for key in MOVED_BEHIND_FULL:
+            assert key not in rec, key
+        assert "kernel_ms_untuned" not in rec["roofline"] and len(rec["placement"]["candidates_ms"]) == 2
+        assert sorted(os.listdir(tmp_path / d)) == ["out_field.npy"]
+        outs.append(np.load(tmp_path / d / "out_field.npy"))
+    a, b = outs
+    assert a.dtype == np.float64 and a.shape == (48_000_000 // 8,)
+    assert np.isfinite(a).all() and np.abs(a).max() <= 80.0 and np.count_nonzero(a) > 0.99 * a.size
+    assert np.array_equal(a, b)
 
 
 @pytest.mark.gpu
