@@ -239,7 +239,14 @@ def from_array(data, dtype=np.float64, *, backend, aligned_index=None, dimension
     As ``storage/cartesian/interface.py:263-327``: ``dtype`` defaults to float64 (``None`` keeps
     the data's dtype); a subarray dtype ``(base, dims)`` takes its data dimensions from the
     trailing axes of ``data``, which must match ``dims``.
+
+    Device data (a CUDA torch tensor or any ``__cuda_array_interface__`` object) on a GPU backend
+    never leaves the device: the cast, if any, runs there and the relayout kernel
+    (``storage/relayout.py``) writes the storage.
     """
+    info = REGISTRY.get(backend)
+    if info is not None and _device_of(info) == "gpu" and _is_device_data(data):
+        return _from_device_array(data, dtype, backend, aligned_index, dimensions)
     if hasattr(data, "detach") and hasattr(data, "cpu"):
         host = data.detach().cpu().numpy()
     else:
@@ -253,6 +260,80 @@ def from_array(data, dtype=np.float64, *, backend, aligned_index=None, dimension
     arr = empty(shape, dtype, backend=backend, aligned_index=aligned_index, dimensions=dimensions)
     _copy_in(arr, host.astype(dtype.base, copy=False))
     return arr
+
+
+def _is_device_data(obj) -> bool:
+    if _is_torch(obj):
+        return bool(getattr(obj, "is_cuda", False))
+    return not isinstance(obj, np.ndarray) and hasattr(obj, "__cuda_array_interface__")
+
+
+def _as_device_tensor(obj):
+    import torch
+
+    return obj.detach() if _is_torch(obj) else torch.as_tensor(obj, device="cuda")
+
+
+def _from_device_array(data, dtype, backend, aligned_index, dimensions):
+    """``from_array`` for device data on a GPU backend: no device->host transfer."""
+    from gt4py_amd.storage import relayout
+
+    src = _as_device_tensor(data)
+    dtype = np.dtype(numpy_dtype_of(src) if dtype is None else dtype)
+    shape = tuple(src.shape)
+    if dtype.shape:
+        if tuple(shape[-dtype.ndim:]) != tuple(dtype.shape):
+            raise ValueError(f"Incompatible data shape {shape} with dtype of shape {dtype.shape}.")
+        shape = shape[: -dtype.ndim]
+    arr = empty(shape, dtype, backend=backend, aligned_index=aligned_index, dimensions=dimensions)
+    if src.device != arr.device:
+        src = src.to(arr.device)
+    relayout.copy(arr, src.to(torch_dtype(dtype.base)))
+    return arr
+
+
+def assign(dst, src, *, stream=None):
+    """Copy ``src`` into the existing storage ``dst`` (same shape; values cast to ``dst``'s dtype
+    as numpy ``astype`` does). Device to device is one relayout kernel on ``stream`` (default:
+    the current stream); every other combination moves through the host like ``from_array`` /
+    ``to_numpy``. Returns ``dst``."""
+    if _is_device_data(src):
+        src = _as_device_tensor(src)
+    src_shape = tuple(src.shape) if hasattr(src, "shape") else np.shape(src)
+    if tuple(dst.shape) != tuple(src_shape):
+        raise ValueError(f"assign: shape {tuple(src_shape)} does not match the storage's {tuple(dst.shape)}")
+    if _is_device_data(src) and _is_device_data(dst):
+        import torch
+
+        from gt4py_amd.storage import relayout
+
+        s = stream if stream is not None else torch.cuda.current_stream(dst.device)
+        with torch.cuda.device(dst.device), torch.cuda.stream(s):  # the cast's temporary lives on `s`
+            if src.device != dst.device:
+                src = src.to(dst.device)
+            relayout.copy(dst, src.to(dst.dtype), stream=s)
+        return dst
+    host = to_numpy(src) if _is_torch(src) else np.asarray(src)
+    _copy_in(dst, host.astype(numpy_dtype_of(dst), copy=False))
+    return dst
+
+
+def contiguous(arr):
+    """A new dense C-order array with ``arr``'s values on the same device: a ``torch.Tensor`` for
+    device storages (one relayout kernel), a numpy array on the host."""
+    if isinstance(arr, np.ndarray):
+        return np.array(arr, order="C", copy=True)
+    if _is_torch(arr):
+        import torch
+
+        if not arr.is_cuda:
+            return arr.detach().clone(memory_format=torch.contiguous_format)
+        from gt4py_amd.storage import relayout
+
+        out = torch.empty(tuple(arr.shape), dtype=arr.dtype, device=arr.device)
+        relayout.copy(out, arr)
+        return out
+    return np.array(np.asarray(arr), order="C", copy=True)
 
 
 def _fill(arr, value):
@@ -365,6 +446,8 @@ __all__ = [
     "ones",
     "full",
     "from_array",
+    "assign",
+    "contiguous",
     "to_numpy",
     "cpu_copy",
     "normalize_storage_spec",
