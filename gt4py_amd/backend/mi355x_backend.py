@@ -165,7 +165,3 @@ class Mi355xBackend(BaseBackend):
         run_impl.bind = compiled.bind  # fast path of repeated calls (stencil_object.py)
         run_impl.supports_rows = True  # gtmi_stencil_run_jsplit
         return run_impl
-
-    def make_stencil_class(self):
-        cls = super().make_stencil_class()
-        return cls

@@ -2,6 +2,9 @@
 
 One thread per (i, j) column, 64 x 4 threads per block; the thread walks the levels of each
 vertical loop of the kernel in loop order. See ``codegen/hip.py`` and DESIGN.md §3.
+``ColumnGen`` plans the kernel (windows, tail cache, register band, tile geometry) and renders its
+frame (parameters, thread-to-column prologue, base pointers, host launch); one ``_LoopRenderer``
+per vertical loop renders the sweep itself.
 
 * **K-windows** -- every accessed ``(name, di, dj)`` has a register window over the K offsets
   it is read at (the register-carried K-cache of the reference's ``KCacheDetection``,
@@ -26,13 +29,13 @@ from __future__ import annotations
 
 import dataclasses
 import re
-from typing import Dict, List, Optional, Set, Tuple
+from typing import Dict, List, NamedTuple, Optional, Set, Tuple
 
 from gt4py_amd import ir
 from gt4py_amd.codegen.plan import ColumnKernel, KernelPlan, UnsupportedStencil, sections_contiguous
 from gt4py_amd.passes import StencilAnalysis, iter_accesses
-from gt4py_amd.codegen.common import (  # noqa: F401
-    COLUMN_BLOCK, ExprRenderer, FieldSlot, cname, host_fill, interval_bounds, kparam_decl, region_condition,
+from gt4py_amd.codegen.common import (
+    COLUMN_BLOCK, ExprRenderer, FieldSlot, cname, host_params, interval_bounds, params_struct, render_stmt, xcd_remap,
 )
 
 LDS_BYTES = 160 * 1024  # per CU (MI355X_MICROARCH.md); one 256-thread block may take all of it
@@ -69,16 +72,25 @@ TILE_LBLOCK = 2
 # 112 x 15 tile -- the only way past the 1024-thread cap to a tile both wide and tall
 TILE_ROWS = 1
 _ROW1 = re.compile(r"\b(w\d+_\w+|rg\d+_\w+|cb_\w+|sn\d+_\w+|j|ty|alive|own)\b")
+_KVAR = re.compile(r"\bk\b")
+_WVAR = re.compile(r"\bw\d+_\w+")
+_WASSIGN = re.compile(r"^\s*(w\d+_\w+) = ")
+_CBVAR = re.compile(r"\bcb_\w+")
 
 
 def _row1(line: str) -> str:
     """Tile mode, a thread's second row: the same code on its own column state (window, ring and
     snapshot registers, column bases, j, ty, alive and own renamed)."""
     return _ROW1.sub(r"\1_r1", line)
-_KVAR = re.compile(r"\bk\b")
-_WVAR = re.compile(r"\bw\d+_\w+")
-_WASSIGN = re.compile(r"^\s*(w\d+_\w+) = ")
-_CBVAR = re.compile(r"\bcb_\w+")
+
+
+def _pmask(lblock: int) -> str:
+    """Tile mode: mask of a level's LDS plane index (the planes rotate over 2 x ``lblock`` buffers)."""
+    return "1" if lblock == 1 else str(2 * lblock - 1)
+
+
+def _indent(lines: List[str], n: int) -> List[str]:
+    return [" " * n + x for x in lines]
 
 
 @dataclasses.dataclass
@@ -111,6 +123,17 @@ class _Tail:
         return f"tl_{cname(name)}"
 
 
+class _LoopText(NamedTuple):
+    """What ``_LoopRenderer.render`` returns."""
+
+    lines: List[str]
+    blocked: bool  # tile mode: some steady-state loop runs several levels per LDS barrier
+    # reader of a register band whose first fronts the writer prefetches: their kernel-scope
+    # declarations, and their loads per band level in sweep order (for the writer's renderer)
+    xpf_decls: List[str]
+    xpf_loads: List[List[str]]
+
+
 class ColumnGen:
     def __init__(self, analysis: StencilAnalysis, plan: KernelPlan, kernel: ColumnKernel, slots, kid, opts):
         self.a = analysis
@@ -139,7 +162,6 @@ class ColumnGen:
         self.lblock = int(opts.get("tile_lblock", TILE_LBLOCK)) if self.tile else 1
         if self.lblock not in (1, 2, 4):
             raise ValueError(f"tile_lblock must be 1, 2 or 4, got {self.lblock}")
-        self.pmask = "1" if self.lblock == 1 else str(2 * self.lblock - 1)
         self._by_cap = 16
         self.trows = int(opts.get("tile_rows", TILE_ROWS)) if self.tile else 1
         if self.trows not in (1, 2):
@@ -157,6 +179,7 @@ class ColumnGen:
         self.kreg = 0
         self.band_pf_default = None
         self.tail = None if self.tile else self._plan_tail()
+        self._scan_accesses()
 
     def _mem(self, name):
         return name in self.api or name in self.scratch
@@ -173,8 +196,7 @@ class ColumnGen:
         still does not fit goes to the staged lowering (UnsupportedStencil)."""
         if self.tile_lds_bytes() <= LDS_BYTES:
             return
-        if self.lblock > 1:
-            self.lblock, self.pmask = 1, "1"
+        self.lblock = 1
         if self.tile_lds_bytes() > LDS_BYTES and int(self.opts.get("tile_by", TILE_BY)) == -1:
             self._by_cap = 8
         if self.tile_lds_bytes() > LDS_BYTES:
@@ -296,7 +318,7 @@ class ColumnGen:
             if vl.loop_order == ir.LoopOrder.PARALLEL and name in wnames and (rng[0] < 0 or rng[1] > 0):
                 if any(_parallel_k_race(sec, name) for sec in vl.sections):
                     raise UnsupportedStencil(f"'{name}' written and read at a K offset in one PARALLEL loop")
-            if not self._mem(name) and rng[0] != rng[1] and not _contiguous(vl):
+            if not self._mem(name) and rng[0] != rng[1] and not sections_contiguous(vl):
                 # the planner puts such temporaries in scratch (plan.make_plan); a register window
                 # cannot carry a value across levels that never run
                 raise UnsupportedStencil(f"register temporary '{name}' read at a K offset across a section gap")
@@ -424,35 +446,30 @@ class ColumnGen:
                     out.add(li)
         return out
 
-    # ------------------------------------------------------------------ rendering
-    def render(self) -> Tuple[str, str]:
-        k = self.kid
-        st = self.st
-        used: List[FieldSlot] = []
-        written: Set[str] = set()
-        for li in self.kernel.loops:
-            for sec in st.vertical_loops[li].sections:
-                for acc, w in iter_accesses(sec.body):
-                    if isinstance(acc, ir.FieldAccess) and self._mem(acc.name):
-                        if self.slots[acc.name] not in used:
-                            used.append(self.slots[acc.name])
-                        if w:
-                            written.add(acc.name)
-        # cache policy: non-temporal loads of read-once streams (never written here, one IJ offset)
-        # and non-temporal stores of fields no other loop of this kernel reads back
+    def _scan_accesses(self) -> None:
+        """The kernel's memory-backed fields (``used`` slots in first-access order, ``written``
+        names) and its cache policy: non-temporal loads of read-once streams (never written here,
+        one IJ offset) and non-temporal stores of fields no other loop of this kernel reads back."""
+        self.used: List[FieldSlot] = []
+        self.written: Set[str] = set()
         keys: Dict[str, Set[Tuple[int, int]]] = {}
         read_loops: Dict[str, Set[int]] = {}
         write_loops: Dict[str, Set[int]] = {}
         for li in self.kernel.loops:
-            for sec in st.vertical_loops[li].sections:
+            for sec in self.st.vertical_loops[li].sections:
                 for acc, w in iter_accesses(sec.body):
                     if not isinstance(acc, ir.FieldAccess):
                         continue
+                    if self._mem(acc.name):
+                        if self.slots[acc.name] not in self.used:
+                            self.used.append(self.slots[acc.name])
+                        if w:
+                            self.written.add(acc.name)
                     (write_loops if w else read_loops).setdefault(acc.name, set()).add(li)
                     if not w:
                         keys.setdefault(acc.name, set()).add(acc.offset[:2])
-        self.nt_loads = set()
-        self.nt_stores = set()
+        self.nt_loads: Set[str] = set()
+        self.nt_stores: Set[str] = set()
         # tile kernels: the halo lanes load the neighbouring tiles' columns, so every stream is read
         # by more than one block and stays cacheable (non-temporal: 1.15x the time, r03l sweep)
         if self.opts.get("nt_load", 0 if self.tile else 1):
@@ -462,30 +479,49 @@ class ColumnGen:
                 n for n, wl in write_loops.items()
                 if self._mem(n) and n not in self.scratch and not (read_loops.get(n, set()) - wl)
             }
-        scalars = st.scalar_params()
-        L = []
-        L.append(f"struct K{k}Params {{")
-        for s in used:
-            L += ["    " + x for x in kparam_decl(s, s.name in written)]
-        for s in scalars:
-            L.append(f"    {s.dtype.ctype} s_{cname(s.name)};")
-        L.append("    int32_t ni, nj, nk;")
-        L.append("    int32_t tail_len;  // levels held in the LDS tail cache (0: none)")
-        L.append("};")
-        L.append("")
+
+    # ------------------------------------------------------------------ rendering
+    def render(self) -> Tuple[str, str]:
+        device = self._render_device(self.lblock)
+        if device is None:  # nothing could be blocked: two planes, as with tile_lblock=1
+            device = self._render_device(1)
+        return device, self._render_host()
+
+    def _render_device(self, lblock: int) -> Optional[str]:
+        """The parameter struct and the kernel with ``lblock`` levels per LDS barrier (tile mode);
+        None when ``lblock`` > 1 and no loop of the kernel could be blocked."""
+        k = self.kid
+        scalars = self.st.scalar_params()
         bx, by = self._block()
+        L = params_struct(k, self.used, self.written, scalars,
+                          ["int32_t ni, nj, nk;", "int32_t tail_len;  // levels held in the LDS tail cache (0: none)"])
         L.append(f"__global__ void __launch_bounds__({bx * by}) k{k}_column(const K{k}Params p) {{")
-        B = []
+        B = self._thread_prologue(lblock)
+        B.append("const int nk = p.nk;")
+        for s in scalars:
+            B.append(f"const {s.dtype.ctype} s_{cname(s.name)} = p.s_{cname(s.name)};")
+        bases = self._base_pointers(B)
+        B += self._tail_prologue()
+        loops = self._render_loops(lblock, bases)
+        if loops is None:
+            return None
+        return "\n".join(L + _indent(B + loops, 4) + ["}"])
+
+    def _thread_prologue(self, lblock: int) -> List[str]:
+        """Thread -> column (i, j): overlapping tiles, XCD-aware block order or the natural one."""
+        bx, by = self._block()
         eilo, eihi, ejlo, ejhi = self.ext
+        leave = f"if (i >= p.ni + {eihi} || j >= p.nj + {ejhi}) return;"
+        if not self.tile and int(self.opts.get("col_order", 1)) != 1:
+            return [f"const int i = (int)(blockIdx.x * {bx} + threadIdx.x) - {eilo};",
+                    f"const int j = (int)(blockIdx.y * {by} + threadIdx.y) - {ejlo};", leave]
+        B = ["const int nbx = (int)gridDim.x, nb = nbx * (int)gridDim.y;",
+             "const int b = (int)(blockIdx.y * gridDim.x + blockIdx.x);"] + xcd_remap("w")
         if self.tile:
             # overlapping tiles: block (ti, tj) owns output columns [ti*TI, ti*TI + TI) x
             # [tj*TJ, tj*TJ + TJ) and its threads cover them plus the loop's IJ extent as halo;
             # no thread returns early (every thread reaches every level's barrier)
             TI, TJ = self._tile_geom()
-            B.append("const int nbx = (int)gridDim.x, nb = nbx * (int)gridDim.y;")
-            B.append("const int b = (int)(blockIdx.y * gridDim.x + blockIdx.x);")
-            B.append("const int q = nb >> 3, r = nb & 7, xcd = b & 7, slot = b >> 3;")
-            B.append("const int w = (xcd < r) ? xcd * (q + 1) + slot : r * (q + 1) + (xcd - r) * q + slot;")
             B.append("const int tx = (int)threadIdx.x, ty = (int)threadIdx.y;")
             # tile order within an XCD's range (option ``tile_order``): 0 I-fast (neighbours in I are
             # consecutive work items), 1 J-fast, 2 pairs of J rows I-fast (tiles (ti, 2q) and (ti, 2q+1)
@@ -504,107 +540,111 @@ class ColumnGen:
             else:
                 B.append(f"const int i = tti * {TI} + tx - {eilo};")
             B.append(f"const int j = ttj * {TJ} + ty - {ejlo};")
-            B.append(f"const bool alive = i < p.ni + {eihi} && j < p.nj + {ejhi};")
-            B.append(f"const bool own = tx >= {eilo} && tx < {eilo + TI} && ty >= {ejlo} && ty < {ejlo + TJ} && "
-                     f"i < p.ni && j < p.nj;")
+            alive = f"const bool alive = i < p.ni + {eihi} && j < p.nj + {ejhi};"
+            own = (f"const bool own = tx >= {eilo} && tx < {eilo + TI} && ty >= {ejlo} && ty < {ejlo + TJ} && "
+                   f"i < p.ni && j < p.nj;")
+            B += [alive, own]
             if self.trows == 2:  # the thread's second row, by rows further down the tile
-                B.append(f"const int ty_r1 = ty + {by}, j_r1 = j + {by};")
-                B.append(_row1(f"const bool alive = i < p.ni + {eihi} && j < p.nj + {ejhi};"))
-                B.append(_row1(f"const bool own = tx >= {eilo} && tx < {eilo + TI} && ty >= {ejlo} && "
-                               f"ty < {ejlo + TJ} && i < p.ni && j < p.nj;"))
+                B += [f"const int ty_r1 = ty + {by}, j_r1 = j + {by};", _row1(alive), _row1(own)]
             for n in sorted(self.lds):
                 ct = self.st.decl(n).dtype.ctype
-                B.append(f"__shared__ {ct} lds_{cname(n)}[{2 * self.lblock}][{by * self.trows}][{bx}];  "
-                         f"// this level's plane (k & {self.pmask})")
-        elif int(self.opts.get("col_order", 1)) == 1:
-            # XCD-aware: consecutive column blocks (along I, then J) run on one XCD (8 XCDs, round-robin dispatch)
-            B.append("const int nbx = (int)gridDim.x, nb = nbx * (int)gridDim.y;")
-            B.append("const int b = (int)(blockIdx.y * gridDim.x + blockIdx.x);")
-            B.append("const int q = nb >> 3, r = nb & 7, xcd = b & 7, slot = b >> 3;")
-            B.append("const int w = (xcd < r) ? xcd * (q + 1) + slot : r * (q + 1) + (xcd - r) * q + slot;")
-            B.append(f"const int i = (w % nbx) * {bx} + (int)threadIdx.x - {eilo};")
-            B.append(f"const int j = (w / nbx) * {by} + (int)threadIdx.y - {ejlo};")
-        else:
-            B.append(f"const int i = (int)(blockIdx.x * {bx} + threadIdx.x) - {eilo};")
-            B.append(f"const int j = (int)(blockIdx.y * {by} + threadIdx.y) - {ejlo};")
-        if not self.tile:
-            B.append(f"if (i >= p.ni + {eihi} || j >= p.nj + {ejhi}) return;")
-        B.append("const int nk = p.nk;")
-        for s in scalars:
-            B.append(f"const {s.dtype.ctype} s_{cname(s.name)} = p.s_{cname(s.name)};")
-        # column base pointers: the i/j part of every address, computed once per thread
-        self.bases: Dict[Tuple[str, int, int], str] = {}
-        nb0 = len(B)
+                B.append(f"__shared__ {ct} lds_{cname(n)}[{2 * lblock}][{by * self.trows}][{bx}];  "
+                         f"// this level's plane (k & {_pmask(lblock)})")
+            return B
+        # XCD-aware: consecutive column blocks (along I, then J) run on one XCD (8 XCDs, round-robin dispatch)
+        return B + [f"const int i = (w % nbx) * {bx} + (int)threadIdx.x - {eilo};",
+                    f"const int j = (w / nbx) * {by} + (int)threadIdx.y - {ejlo};", leave]
+
+    def _base_pointers(self, B: List[str]) -> Dict[Tuple[str, int, int], str]:
+        """Column base pointers: the i/j part of every address, computed once per thread. Appends
+        their declarations to ``B``; returns (name, di, dj) -> variable."""
+        keys = []
         for li in self.kernel.loops:
             inf = self.info[li]
-            for (name, di, dj) in list(inf.win) + [(n, None, None) for n in sorted(inf.direct)]:
-                if not self._mem(name):
-                    continue
-                if di is None:
-                    continue  # direct accesses: offsets known per access, see _base()
-                self._base(name, di, dj, B, name in written)
-            for sec in self.st.vertical_loops[li].sections:
-                for acc, w in iter_accesses(sec.body):
-                    if isinstance(acc, ir.FieldAccess) and acc.name in inf.direct:
-                        self._base(acc.name, acc.offset[0], acc.offset[1], B, acc.name in written)
-        if self.trows == 2:
-            B += [_row1(x) for x in B[nb0:]]
-        if self.tail is not None:
-            t = self.tail
-            B.append(f"extern __shared__ __attribute__((aligned(16))) char gtmi_lds[];")
-            B.append(f"const int tid = (int)(threadIdx.y * {bx} + threadIdx.x);")
-            if self.kreg:
-                R = self.kreg
-                B.append(f"const bool regband = nk >= {self.band_nmin};  // register band of {R} levels")
-                B.append(f"const int rbase = regband ? {R} : 0;")
-                for n in t.fields:
-                    ct = self.st.decl(n).dtype.ctype
-                    B.append(f"{ct} " + ", ".join(f"rb_{cname(n)}_{u}" for u in range(R)) + ";")
-            else:
-                B.append("const int rbase = 0;")
-            B.append("const int tlen = p.tail_len < nk - rbase ? p.tail_len : nk - rbase;")
-            if not t.low:
-                B.append("const int tc1 = nk - rbase, tc0 = tc1 - tlen;  // LDS-cached levels [tc0, tc1)")
-            else:
-                B.append("const int tc0 = rbase, tc1 = rbase + tlen;  // LDS-cached levels [tc0, tc1)")
-            off = "0"
+            keys += [key for key in inf.win if self._mem(key[0])]
+            for sec in self.st.vertical_loops[li].sections:  # direct accesses: offsets known per access
+                keys += [(acc.name, *acc.offset[:2]) for acc, _ in iter_accesses(sec.body)
+                         if isinstance(acc, ir.FieldAccess) and acc.name in inf.direct]
+        bases: Dict[Tuple[str, int, int], str] = {}
+        decls = []
+        for key in keys:
+            if key in bases:
+                continue
+            name, di, dj = key
+            c = cname(name)
+            bases[key] = f"cb_{c}_{_sgn(di)}_{_sgn(dj)}"
+            decls.append(
+                f"{'' if name in self.written else 'const '}{self.st.decl(name).dtype.ctype}* __restrict__ {bases[key]} = "
+                f"p.p_{c} + ((int64_t)gtmi::clampi(i + ({di}), p.ilo_{c}, p.ihi_{c}) * "
+                f"p.sI_{c} + (int64_t)gtmi::clampi(j + ({dj}), p.jlo_{c}, p.jhi_{c}) * p.sJ_{c});"
+            )
+        B += decls + ([_row1(x) for x in decls] if self.trows == 2 else [])
+        return bases
+
+    def _tail_prologue(self) -> List[str]:
+        """The LDS tail cache's level range and per-field arrays, the register band's registers."""
+        t = self.tail
+        if t is None:
+            return []
+        bx, _ = self._block()
+        B = ["extern __shared__ __attribute__((aligned(16))) char gtmi_lds[];",
+             f"const int tid = (int)(threadIdx.y * {bx} + threadIdx.x);"]
+        if self.kreg:
+            R = self.kreg
+            B.append(f"const bool regband = nk >= {self.band_nmin};  // register band of {R} levels")
+            B.append(f"const int rbase = regband ? {R} : 0;")
             for n in t.fields:
                 ct = self.st.decl(n).dtype.ctype
-                B.append(f"{ct}* __restrict__ {t.var(n)} = ({ct}*)(gtmi_lds + {off});")
-                off = f"{off} + (size_t)p.tail_len * 256 * sizeof({ct})"
-        # prefetch across the writer/reader boundary of the register band: the
-        # reader is rendered first so that the writer's last band levels can issue the reader's
-        # first band prefetches (declared here, at kernel scope)
-        t_ = self.tail
-        self._xpf = bool(self.kreg) and t_ is not None and not t_.head \
-            and t_.a != t_.b and t_.b in self.kernel.loops and t_.a in self.kernel.loops \
-            and self.kernel.loops.index(t_.b) == self.kernel.loops.index(t_.a) + 1
-        if self._xpf:
+                B.append(f"{ct} " + ", ".join(f"rb_{cname(n)}_{u}" for u in range(R)) + ";")
+        else:
+            B.append("const int rbase = 0;")
+        B.append("const int tlen = p.tail_len < nk - rbase ? p.tail_len : nk - rbase;")
+        if not t.low:
+            B.append("const int tc1 = nk - rbase, tc0 = tc1 - tlen;  // LDS-cached levels [tc0, tc1)")
+        else:
+            B.append("const int tc0 = rbase, tc1 = rbase + tlen;  // LDS-cached levels [tc0, tc1)")
+        off = "0"
+        for n in t.fields:
+            ct = self.st.decl(n).dtype.ctype
+            B.append(f"{ct}* __restrict__ {t.var(n)} = ({ct}*)(gtmi_lds + {off});")
+            off = f"{off} + (size_t)p.tail_len * 256 * sizeof({ct})"
+        return B
+
+    def _render_loops(self, lblock: int, bases) -> Optional[List[str]]:
+        """Every vertical loop of the kernel in order; None when ``lblock`` > 1 blocked nothing."""
+        t, loops = self.tail, self.kernel.loops
+        # prefetch across the writer/reader boundary of the register band: the reader is rendered
+        # first so that the writer's last band levels can issue the reader's first band prefetches
+        # (declared at kernel scope)
+        xpf = bool(self.kreg) and t is not None and not t.head and t.a != t.b and t.b in loops and t.a in loops \
+            and loops.index(t.b) == loops.index(t.a) + 1
+        if xpf:
             # a reader front the writer's band might still write (any reader window field the
             # writer writes, except the band-served tail fields) must not be fetched early
-            wa = self.info[t_.a]
-            clash = {n for (n, _, _) in self.info[t_.b].win} & (wa.wnames | wa.direct)
-            self._xpf = not (clash - set(t_.fields))
-        self._xpf_decls, self._xpf_loads = [], []
-        order = [t_.b] + [x for x in self.kernel.loops if x != t_.b] if self._xpf else list(self.kernel.loops)
-        self._blocked_any = False
-        rendered = {li: self._render_loop(li) for li in order}
-        if self.lblock > 1 and not self._blocked_any:
-            # nothing could be blocked: two planes, as with tile_lblock=1
-            self.lblock, self.pmask = 1, "1"
-            return self.render()
-        B += self._xpf_decls
-        for li in self.kernel.loops:
-            B += rendered[li]
-        L += ["    " + x for x in B]
-        L.append("}")
+            wa = self.info[t.a]
+            clash = {n for (n, _, _) in self.info[t.b].win} & (wa.wnames | wa.direct)
+            xpf = not (clash - set(t.fields))
+        rendered: Dict[int, _LoopText] = {}
+        if xpf:
+            rendered[t.b] = _LoopRenderer(self, t.b, lblock, bases, hands_off=True).render()
+        for li in loops:
+            if li not in rendered:
+                reader_loads = rendered[t.b].xpf_loads if xpf and li == t.a else None
+                rendered[li] = _LoopRenderer(self, li, lblock, bases, reader_loads=reader_loads).render()
+        if lblock > 1 and not any(r.blocked for r in rendered.values()):
+            return None
+        B = list(rendered[t.b].xpf_decls) if xpf else []
+        for li in loops:
+            B += rendered[li].lines
+        return B
+
+    def _render_host(self) -> str:
+        k = self.kid
+        bx, by = self._block()
+        eilo, eihi, ejlo, ejhi = self.ext
         H = [f"{{  // kernel {k}: column, loops {self.kernel.loops}"]
         H.append("    if (ni > 0 && nj > 0 && nk > 0) {")
-        H.append(f"        K{k}Params p;")
-        for s in used:
-            H += ["        " + x for x in host_fill(s, "p", s.name in written)]
-        for i_s, s in enumerate(scalars):
-            H.append(f"        memcpy(&p.s_{cname(s.name)}, &sc[{i_s}], sizeof(p.s_{cname(s.name)}));")
+        H += _indent(host_params(k, self.used, self.written, self.st.scalar_params()), 8)
         H.append("        p.ni = ni; p.nj = nj; p.nk = nk;")
         lds = "0"
         if self.tail is not None:
@@ -630,614 +670,567 @@ class ColumnGen:
             H.append(f"        hipLaunchKernelGGL(k{k}_column, {grid});")
         H.append("    }")
         H.append("}")
-        return "\n".join(L), "\n".join(H)
+        return "\n".join(H)
 
-    def _base_fields(self) -> Dict[str, str]:
-        """Column base pointer variable -> the field it addresses."""
-        return {v: key[0] for key, v in self.bases.items()}
 
-    @staticmethod
-    def _blockable(levels: List[List[str]], shift: List[str], base_fields: Optional[Dict[str, str]] = None) -> bool:
-        """Can a level's statements after its LDS barrier wait until the next level's statements
-        before it have run? Exactly one barrier per level, no plane written after it, no window
-        value assigned after it that the next level's shift or statements read, and no field
-        stored to memory after it that the next level's shift or statements load (the caller also
-        refuses loops with run-time K offsets, whose memory reads this text test cannot place)."""
-        st = levels[0]
-        bars = [q for q, x in enumerate(st) if x.startswith("gtmi::lds_barrier();")]
-        if len(bars) != 1:
+def _blockable(levels: List[List[str]], shift: List[str], base_fields: Optional[Dict[str, str]] = None) -> bool:
+    """Can a level's statements after its LDS barrier wait until the next level's statements
+    before it have run? Exactly one barrier per level, no plane written after it, no window
+    value assigned after it that the next level's shift or statements read, and no field
+    stored to memory after it that the next level's shift or statements load (the caller also
+    refuses loops with run-time K offsets, whose memory reads this text test cannot place)."""
+    st = levels[0]
+    bars = [q for q, x in enumerate(st) if x.startswith("gtmi::lds_barrier();")]
+    if len(bars) != 1:
+        return False
+    post = st[bars[0] + 1:]
+    if any("lds_" in x and "] = " in x for x in post):
+        return False
+    assigned = {m.group(1) for x in post for m in [_WASSIGN.match(x)] if m}
+    later = "\n".join(shift + levels[1][:bars[0]])
+    if any(re.search(r"\b" + re.escape(n) + r"\b", later) for n in assigned):
+        return False
+    if base_fields:
+        stored = {base_fields[v] for x in post if "sstore<" in x for v in _CBVAR.findall(x) if v in base_fields}
+        loaded = {base_fields[v] for v in _CBVAR.findall(later) if v in base_fields}
+        if stored & loaded:
             return False
-        post = st[bars[0] + 1:]
-        if any("lds_" in x and "] = " in x for x in post):
-            return False
-        assigned = {m.group(1) for x in post for m in [_WASSIGN.match(x)] if m}
-        later = "\n".join(shift + levels[1][:bars[0]])
-        if any(re.search(r"\b" + re.escape(n) + r"\b", later) for n in assigned):
-            return False
-        if base_fields:
-            stored = {base_fields[v] for x in post if "sstore<" in x for v in _CBVAR.findall(x) if v in base_fields}
-            loaded = {base_fields[v] for v in _CBVAR.findall(later) if v in base_fields}
-            if stored & loaded:
-                return False
-        return True
+    return True
 
-    def _base(self, name, di, dj, out: List[str], writable: bool) -> str:
-        key = (name, di, dj)
-        if key not in self.bases:
-            c = cname(name)
-            v = f"cb_{c}_{_sgn(di)}_{_sgn(dj)}"
-            t = self.st.decl(name).dtype.ctype
-            const = "" if writable else "const "
-            out.append(
-                f"{const}{t}* __restrict__ {v} = p.p_{c} + ((int64_t)gtmi::clampi(i + ({di}), p.ilo_{c}, p.ihi_{c}) * "
-                f"p.sI_{c} + (int64_t)gtmi::clampi(j + ({dj}), p.jlo_{c}, p.jhi_{c}) * p.sJ_{c});"
-            )
-            self.bases[key] = v
-        return self.bases[key]
 
-    def _render_loop(self, li) -> List[str]:
-        vl = self.st.vertical_loops[li]
-        order = vl.loop_order
-        info = self.info[li]
-        fwd = info.fwd
-        direct, win, wnames = info.direct, info.win, info.wnames
-        self.direct = direct
-        tail = self.tail
-        tail_write = tail.fields if (tail is not None and tail.a == li) else []
-        tail_read = set(tail.fields) if (tail is not None and tail.b == li) else set()
-        no_store = tail.no_store if (tail is not None and tail.a == li) else set()
-        R = self.kreg if (tail is not None and li in (tail.a, tail.b)) else 0
-        band_map = self.band_map[li] if R else None
-        decl_dtype = {}
-        for (name, di, dj) in win:
-            decl_dtype[name] = self.st.decl(name).dtype
-        for name in direct:
-            decl_dtype[name] = self.st.decl(name).dtype
+class _LoopRenderer:
+    """The text of vertical loop ``li`` of ``gen``'s kernel. The constructor fixes the per-loop
+    facts (tail-cache roles, window fronts, ring keys, the register band's prefetch schedule);
+    ``render`` walks the sections. A level is generated either inside a section's loops
+    (``reg`` None) or as register-band level ``reg`` in the unrolled band code.
 
-        def wvar(name, di, dj, d):
-            rng = win[(name, di, dj)]
-            return f"w{li}_{cname(name)}_{_sgn(di)}_{_sgn(dj)}_{d - rng[0]}"
+    ``lblock``: levels per LDS barrier (tile mode); ``bases``: the kernel's column base pointers;
+    ``hands_off``: this loop reads a register band whose first fronts the writer prefetches
+    (they come back in ``_LoopText.xpf_*``); ``reader_loads``: this loop writes that band and
+    issues these loads of the reader (None: no hand-over)."""
 
-        def mem_ptr(name, di, dj, kexpr):
-            c = cname(name)
-            return f"({self.bases[(name, di, dj)]} + (int64_t)gtmi::clampi({kexpr}, p.klo_{c}, p.khi_{c}) * p.sK_{c})"
-
-        def mem_index(name, di, dj, kexpr):
-            """A load expression (non-temporal for read-once streams)."""
-            nt = "true" if (name in self.nt_loads and name not in direct) else "false"
-            return f"gtmi::sload<{decl_dtype[name].ctype}, {nt}>({mem_ptr(name, di, dj, kexpr)})"
-
-        def load_into(var, name, di, dj, kexpr, maybe_cached=True, reg=None) -> List[str]:
-            """``var = F(level kexpr)``: from the LDS tail cache when this loop reads a cached level
-            (a run-time test unless ``maybe_cached`` is False: the level is known not to be cached);
-            ``reg``: the level's static register-band index (register band levels only)."""
-            if reg is not None and name in tail_read and (di, dj) == (0, 0) and 0 <= reg < R:
-                return [f"{var} = rb_{cname(name)}_{reg};"]
-            if maybe_cached and name in tail_read and (di, dj) == (0, 0):
-                return [
-                    f"{{ const int lv_ = {kexpr};",
-                    f"  if (lv_ >= tc0 && lv_ < tc1) {var} = {tail.var(name)}[(lv_ - tc0) * 256 + tid];",
-                    f"  else {var} = {mem_index(name, di, dj, 'lv_')}; }}",
-                ]
-            return [f"{var} = {mem_index(name, di, dj, kexpr)};"]
-
-        reg_now = [None]  # static register-band index of the level being generated
-        band_now = [None]  # tail writer: None = run-time test per level, True/False = levels known in/out of the cache
-
-        def mem_store(name, kexpr, value):
-            nt = "true" if (name in self.nt_stores and name not in direct) else "false"
-            st = f"gtmi::sstore<{decl_dtype[name].ctype}, {nt}>({mem_ptr(name, 0, 0, kexpr)}, {value});"
-            if name in no_store and kexpr == "k":
-                if band_now[0] == "reg":
-                    return "// register band level: kept in registers only"
-                if band_now[0] is True:
-                    return "// cached level: kept in LDS only"
-                if band_now[0] is None:
-                    st = f"if (k < tc0 || k >= tc1) {st}"
-            return st
-
-        P = self.ring
-        step = "+" if fwd else "-"
-
-        def dup(code: List[str]) -> List[str]:
-            """Per-column code for every row of the thread (tile_rows)."""
-            return code + [_row1(x) for x in code] if self.trows == 2 else code
-
-        def merged(stmts: List[str]) -> List[str]:
-            """A level's statements for every row of the thread, interleaved between the LDS
-            barriers (both rows' planes are written before any row reads across columns); the
-            level's ``k_next`` update (stmts[0]) once."""
-            if self.trows == 1:
-                return stmts
-            chunks, cur = [], []
-            for x in stmts[1:]:
-                if x.startswith("gtmi::lds_barrier();"):
-                    chunks.append((cur, x))
-                    cur = []
-                else:
-                    cur.append(x)
-            res = stmts[:1]
-            for c, bar in chunks:
-                res += c + [_row1(x) for x in c] + [bar]
-            return res + cur + [_row1(x) for x in cur]
-
-        out = [f"{{  // vertical loop {li} ({order.name})"]
-        decls = []
-        for (name, di, dj), rng in win.items():
-            t = decl_dtype[name].ctype
-            for d in range(rng[0], rng[1] + 1):
-                decls.append(f"    {t} {wvar(name, di, dj, d)} = ({t})0;")
-        out += dup(decls)
-        out.append("    int k_next = -0x7fffffff;")
-        front = {}
-        for key, rng in win.items():
-            front[key] = rng[1] if fwd else rng[0]
-
-        def zero_needed_in(name, di, dj, sec) -> bool:
-            """Is entry d == 0 of the window read at this level before an unconditional write?"""
-            if not self._mem(name):
-                return False
-            if (di, dj) != (0, 0) or name not in wnames:
-                return True
-            for s in sec.body:
-                for acc, w in iter_accesses([s]):
-                    if acc.name == name and isinstance(acc, ir.FieldAccess) and acc.offset == (0, 0, 0):
-                        if w:
-                            return not isinstance(s, ir.Assign)
-                        return True
-            return True
-
+    def __init__(self, gen: ColumnGen, li: int, lblock: int, bases, hands_off=False, reader_loads=None):
+        self.g, self.li, self.lblock, self.bases = gen, li, lblock, bases
+        self.hands_off, self.reader_loads = hands_off, reader_loads
+        self.vl = gen.st.vertical_loops[li]
+        info = gen.info[li]
+        self.fwd, self.direct, self.win, self.wnames = info.fwd, info.direct, info.win, info.wnames
+        fwd, win = self.fwd, self.win
+        self.step = "+" if fwd else "-"
+        tail = self.tail = gen.tail
+        self.tail_write = tail.fields if (tail is not None and tail.a == li) else []
+        self.tail_read = set(tail.fields) if (tail is not None and tail.b == li) else set()
+        self.no_store = tail.no_store if (tail is not None and tail.a == li) else set()
+        self.R = gen.kreg if (tail is not None and li in (tail.a, tail.b)) else 0  # register band levels
+        self.band_map = gen.band_map[li] if self.R else None
+        self.decl_dtype = {name: gen.st.decl(name).dtype for name in [key[0] for key in win] + list(self.direct)}
+        self.front = {key: rng[1] if fwd else rng[0] for key, rng in win.items()}
         # which window fronts are loaded from memory at every level (loop-wide decision)
-        front_load = {}
+        self.front_load = {}
         for key in win:
             name, di, dj = key
-            fd = front[key]
-            if not self._mem(name):
-                front_load[key] = False
-            elif fd == 0 and name in wnames:
-                front_load[key] = any(zero_needed_in(name, di, dj, sec) for sec in vl.sections)
+            if not gen._mem(name):
+                self.front_load[key] = False
+            elif self.front[key] == 0 and name in self.wnames:
+                self.front_load[key] = any(self.zero_needed_in(name, di, dj, sec) for sec in self.vl.sections)
             else:
-                front_load[key] = True
+                self.front_load[key] = True
         # ring keys: every loaded front, except fields this loop writes that have no K axis (IJ
         # temporaries/fields: every level is the same address, so a front fetched ahead would
         # miss the writes of the levels in between)
-        ring_keys = [
-            key for key, fl in front_load.items()
-            if fl and not (key[0] in wnames and "K" not in self.st.decl(key[0]).axes)
-        ] if P > 1 else []
+        self.ring_keys = [key for key, fl in self.front_load.items() if fl and not self._ij_written(key)] \
+            if gen.ring > 1 else []
         # fronts of tail-cached fields in the reading loop (LDS source in the cached segment)
-        tail_keys = [key for key, fl in front_load.items() if fl and key[0] in tail_read and key[1:] == (0, 0)]
+        self.tail_keys = [key for key, fl in self.front_load.items()
+                          if fl and key[0] in self.tail_read and key[1:] == (0, 0)]
+        self.rend = ExprRenderer(self.resolve, lambda n: f"s_{cname(n)}", lambda ax: ["i", "j", "k"][ax])
+        self.rend.exact_fma = bool(int(gen.opts.get("exact_fma", 1)))
+        if self.R:
+            self._plan_band_prefetch()
 
+    def _ij_written(self, key) -> bool:
+        return key[0] in self.wnames and "K" not in self.g.st.decl(key[0]).axes
+
+    def _plan_band_prefetch(self) -> None:
+        """Register band fronts prefetched across the whole band: one sweep-order list of band
+        levels over all sections (``all_us``), each level prefetching the one ``Pb`` levels on
+        whatever section it lies in, and -- for the writer, whose band ends the sweep -- the prologue
+        issued at the start of the loop, so no band level (nor the first) waits for loads issued
+        at a section boundary."""
+        g, R = self.g, self.R
+        ring_pf = g.ring + BAND_PF_OVER_RING
+        Pb = self.Pb = int(g.opts.get("kreg_pf", g.band_pf_default if g.band_pf_default is not None else ring_pf))
+        all_us = self.all_us = sorted((u for u in range(R) if self.band_map[u] is not None), reverse=not self.fwd)
+        self.mem_keys = {}  # band level -> the fronts it loads from memory
+        for u in all_us:
+            mk = []
+            for key in self.win:
+                if not self.front_load[key] or not g._mem(key[0]):
+                    continue
+                if self._ij_written(key):
+                    continue  # as ring_keys: one address for every level, loaded at its level
+                if key[0] in self.tail_read and key[1:] == (0, 0) and 0 <= u + self.front[key] < R:
+                    continue  # served by the register band
+                mk.append(key)
+            self.mem_keys[u] = mk
+        self.pfv = {(u, key): f"bp{u}_{self.wvar(*key, self.front[key])}" for u in all_us for key in self.mem_keys[u]}
+        # span schedule: ``pre`` levels are in flight when the band starts (the prologue, or for
+        # the reader the writer's last levels: at most the default distance, which the writer's
+        # registers afford); the rest are issued at most two per level, each ``Pb`` levels
+        # ahead or as early as that allows, so a deeper distance ramps up within the band
+        self.issue_at: Dict[int, List[int]] = {}
+        self.pre = 0
+        if Pb > 0:
+            pre = min(Pb, int(g.opts.get("kreg_pf", ring_pf))) if self.hands_off else Pb
+            pre = self.pre = min(pre, len(all_us))
+            pend = list(range(pre, len(all_us)))
+            for p_ in range(len(all_us)):
+                while pend and pend[0] - Pb <= p_ and len(self.issue_at.get(p_, ())) < 2:
+                    self.issue_at.setdefault(p_, []).append(pend.pop(0))
+
+    # ------------------------------------------------------------------ names, loads and stores
+    def wvar(self, name, di, dj, d) -> str:
+        return f"w{self.li}_{cname(name)}_{_sgn(di)}_{_sgn(dj)}_{d - self.win[(name, di, dj)][0]}"
+
+    def mem_ptr(self, name, di, dj, kexpr) -> str:
+        c = cname(name)
+        return f"({self.bases[(name, di, dj)]} + (int64_t)gtmi::clampi({kexpr}, p.klo_{c}, p.khi_{c}) * p.sK_{c})"
+
+    def mem_index(self, name, di, dj, kexpr) -> str:
+        """A load expression (non-temporal for read-once streams)."""
+        nt = "true" if (name in self.g.nt_loads and name not in self.direct) else "false"
+        return f"gtmi::sload<{self.decl_dtype[name].ctype}, {nt}>({self.mem_ptr(name, di, dj, kexpr)})"
+
+    def load_into(self, var, name, di, dj, kexpr, maybe_cached=True, reg=None) -> List[str]:
+        """``var = F(level kexpr)``: from the LDS tail cache when this loop reads a cached level
+        (a run-time test unless ``maybe_cached`` is False: the level is known not to be cached);
+        ``reg``: the level's static register-band index (register band levels only)."""
+        if reg is not None and name in self.tail_read and (di, dj) == (0, 0) and 0 <= reg < self.R:
+            return [f"{var} = rb_{cname(name)}_{reg};"]
+        if maybe_cached and name in self.tail_read and (di, dj) == (0, 0):
+            return [
+                f"{{ const int lv_ = {kexpr};",
+                f"  if (lv_ >= tc0 && lv_ < tc1) {var} = {self.tail.var(name)}[(lv_ - tc0) * 256 + tid];",
+                f"  else {var} = {self.mem_index(name, di, dj, 'lv_')}; }}",
+            ]
+        return [f"{var} = {self.mem_index(name, di, dj, kexpr)};"]
+
+    def mem_store(self, name, kexpr, value, reg) -> str:
+        """Store at level ``kexpr``; write-free tail fields skip the levels kept on chip (``reg``:
+        the level's register-band index, None for a level whose place is known only at run time)."""
+        nt = "true" if (name in self.g.nt_stores and name not in self.direct) else "false"
+        st = f"gtmi::sstore<{self.decl_dtype[name].ctype}, {nt}>({self.mem_ptr(name, 0, 0, kexpr)}, {value});"
+        if name in self.no_store and kexpr == "k":
+            if reg is not None:
+                return "// register band level: kept in registers only"
+            st = f"if (k < tc0 || k >= tc1) {st}"
+        return st
+
+    def kaddr(self, acc: ir.FieldAccess) -> str:
+        kexpr = f"k + ({acc.offset[2]})"
+        if acc.k_offset is not None:
+            kexpr += f" + (int)({self.rend(acc.k_offset)})"
+        return kexpr
+
+    def resolve(self, acc: ir.FieldAccess) -> str:
+        di, dj, dk = acc.offset
+        if acc.name in self.direct:
+            return self.mem_index(acc.name, di, dj, self.kaddr(acc))
+        if acc.name in self.g.lds and (di or dj):
+            return f"lds_{cname(acc.name)}[k & {_pmask(self.lblock)}][ty + ({dj})][tx + ({di})]"
+        return self.wvar(acc.name, di, dj, dk)
+
+    def dup(self, code: List[str]) -> List[str]:
+        """Per-column code for every row of the thread (tile_rows)."""
+        return code + [_row1(x) for x in code] if self.g.trows == 2 else code
+
+    def merged(self, stmts: List[str]) -> List[str]:
+        """A level's statements for every row of the thread, interleaved between the LDS
+        barriers (both rows' planes are written before any row reads across columns); the
+        level's ``k_next`` update (stmts[0]) once."""
+        if self.g.trows == 1:
+            return stmts
+        chunks, cur = [], []
+        for x in stmts[1:]:
+            if x.startswith("gtmi::lds_barrier();"):
+                chunks.append((cur, x))
+                cur = []
+            else:
+                cur.append(x)
+        res = stmts[:1]
+        for c, bar in chunks:
+            res += c + [_row1(x) for x in c] + [bar]
+        return res + cur + [_row1(x) for x in cur]
+
+    def zero_needed_in(self, name, di, dj, sec) -> bool:
+        """Is entry d == 0 of the window read at this level before an unconditional write?"""
+        if not self.g._mem(name):
+            return False
+        if (di, dj) != (0, 0) or name not in self.wnames:
+            return True
+        for s in sec.body:
+            for acc, w in iter_accesses([s]):
+                if acc.name == name and isinstance(acc, ir.FieldAccess) and acc.offset == (0, 0, 0):
+                    if w:
+                        return not isinstance(s, ir.Assign)
+                    return True
+        return True
+
+    # ------------------------------------------------------------------ one level
+    def shift_and_fronts(self, slot: Optional[int], mode: str, reg_u: Optional[int] = None,
+                         pf: Optional[Dict] = None) -> List[str]:
+        """Shift every window one level and load each front: from ring ``slot``, from the
+        LDS tail cache (``mode`` "lds"), from the register band (``reg_u``: the level's band
+        index), from a band prefetch register (``pf``: key -> variable) or from memory here
+        (``slot`` None)."""
+        body = []
+        for key, rng in self.win.items():
+            name, di, dj = key
+            ds = list(range(rng[0], rng[1] + 1))
+            if self.fwd:
+                for d in ds[:-1]:
+                    body.append(f"{self.wvar(name, di, dj, d)} = {self.wvar(name, di, dj, d + 1)};")
+            else:
+                for d in reversed(ds[1:]):
+                    body.append(f"{self.wvar(name, di, dj, d)} = {self.wvar(name, di, dj, d - 1)};")
+            if self.front_load[key]:
+                fd = self.front[key]
+                fv = self.wvar(name, di, dj, fd)
+                if pf is not None and key in pf:
+                    body.append(f"{fv} = {pf[key]};")
+                elif reg_u is not None:
+                    body += self.load_into(fv, name, di, dj, f"k + ({fd})", maybe_cached=False, reg=reg_u + fd)
+                elif mode == "lds" and key in self.tail_keys:
+                    body.append(f"{fv} = {self.tail.var(name)}[(k + ({fd}) - tc0) * 256 + tid];")
+                elif slot is not None and key in self.ring_keys:
+                    body.append(f"{fv} = rg{slot}_{fv};")
+                else:
+                    body += self.load_into(fv, name, di, dj, f"k + ({fd})", maybe_cached=(mode == "mixed"))
+        return body
+
+    def reload(self, sec, reg_u: Optional[int] = None, pf: Optional[Dict] = None) -> List[str]:
+        """Load the full K-window at a level of section ``sec``."""
+        body = []
+        for (name, di, dj), rng in self.win.items():
+            if not self.g._mem(name):
+                continue
+            for d in range(rng[0], rng[1] + 1):
+                if d == 0 and not self.zero_needed_in(name, di, dj, sec):
+                    continue
+                if pf is not None and (name, di, dj) in pf and d == self.front[(name, di, dj)]:
+                    body.append(f"{self.wvar(name, di, dj, d)} = {pf[(name, di, dj)]};")  # prefetched
+                    continue
+                body += self.load_into(self.wvar(name, di, dj, d), name, di, dj, f"k + ({d})",
+                                       reg=None if reg_u is None else reg_u + d)
+        return body
+
+    def refill(self, slot, ring, keys) -> List[str]:
+        body = []
+        for key in keys:
+            fv = self.wvar(*key, self.front[key])
+            body += self.load_into(f"rg{slot}_{fv}", *key, f"k {self.step} {ring} + ({self.front[key]})", maybe_cached=False)
+        return body
+
+    def assign(self, s, reg) -> List[str]:
+        if not isinstance(s, ir.Assign):
+            raise TypeError(type(s))
+        g, name = self.g, s.target.name
+
+        def stored(st):  # API outputs: each column has one owner / lies inside the domain
+            if name in g.api and g.tile:
+                return f"if (own) {st}"
+            if name in g.api and any(g.ext):
+                return f"if (i >= 0 && i < p.ni && j >= 0 && j < p.nj) {st}"
+            return st
+
+        if name in self.direct:
+            return [stored(self.mem_store(name, self.kaddr(s.target), self.rend(s.value), reg))]
+        tgt = self.wvar(name, 0, 0, 0)
+        out = [f"{tgt} = {self.rend(s.value)};"]
+        if name in g.lds:
+            out.append(f"lds_{cname(name)}[k & {_pmask(self.lblock)}][ty][tx] = {tgt};")
+        if g._mem(name):
+            out.append(stored(self.mem_store(name, "k", tgt, reg)))
+        return out
+
+    def statements(self, si, sec, reg: Optional[int] = None) -> List[str]:
+        """The statements of section ``si`` at level ``k`` (``reg``: as register-band level ``reg``)."""
+        g, li = self.g, self.li
+        body = [f"k_next = k {self.step} 1;"]
+        pending: Set[str] = set()  # LDS planes written since the last barrier (tile mode)
+        for ti, s in enumerate(sec.body):
+            if g.lds:
+                reads = {a.name for a, w in iter_accesses([s])
+                         if not w and isinstance(a, ir.FieldAccess) and a.name in g.lds
+                         and (a.offset[0] or a.offset[1])}
+                if reads & pending:
+                    body.append("gtmi::lds_barrier();  // the level's planes are complete")
+                    pending.clear()
+            code = render_stmt(s, self.rend, lambda x: self.assign(x, reg), "i", "j")
+            guard = g._guard(li, si, ti)
+            if g.tile and any(w and g._mem(a.name) and a.name not in g.api for a, w in iter_accesses([s])):
+                guard = f"{guard} && {g._tile_local(li, si, ti)}" if guard else g._tile_local(li, si, ti)
+            if guard:
+                code = [f"if ({guard}) {{"] + _indent(code, 4) + ["}"]
+            body += code
+            if g.lds:
+                pending |= {a.name for a, w in iter_accesses([s]) if w and a.name in g.lds}
+        if pending:
+            # planes written but not read across columns at this level: the next write of
+            # the same buffer (two levels on) must not overtake a slow reader
+            body.append("gtmi::lds_barrier();")
+        if self.tail_write and reg is not None:
+            body.append("// register band: this level's final values")
+            body += [f"rb_{cname(n)}_{reg} = {self.wvar(n, 0, 0, 0)};" for n in self.tail_write]
+        elif self.tail_write:
+            body.append("if (k >= tc0 && k < tc1) {  // LDS tail cache: this level's final values")
+            body += [f"    {self.tail.var(n)}[(k - tc0) * 256 + tid] = {self.wvar(n, 0, 0, 0)};" for n in self.tail_write]
+            body.append("}")
+        return body
+
+    def level(self, si, sec, slot, mode) -> List[str]:
+        """A level that continues the sweep: shift, fronts (ring ``slot``), statements."""
+        return self.dup(self.shift_and_fronts(slot, mode)) + self.merged(self.statements(si, sec))
+
+    def entry_level(self, si, sec, slot, mode) -> List[str]:
+        """A segment's first level, which may follow a gap: full window reload unless it
+        continues the sweep (the only level with loads inside a branch)."""
+        return (["if (k != k_next) {  // (re)load the full K-window"] + _indent(self.dup(self.reload(sec)), 4)
+                + ["} else {"] + _indent(self.dup(self.shift_and_fronts(slot, mode)), 4) + ["}"]
+                + self.merged(self.statements(si, sec)))
+
+    # ------------------------------------------------------------------ segments and sections
+    def segment(self, si, sec, ss, se, mode: str) -> Tuple[List[str], bool]:
+        """Levels [ss, se) of section ``si`` in sweep order. ``mode``: "mem" (no front of
+        these levels is tail-cached), "lds" (every tail-cached front is), "mixed". Also returns
+        whether the steady-state loop runs several levels per LDS barrier."""
+        fwd, step = self.fwd, self.step
+        keys = [k_ for k_ in self.ring_keys if not (mode == "lds" and k_ in self.tail_keys)] if mode != "mixed" else []
+        ring = _section_ring(sec.interval, self.g.ring) if keys else 0
+        o = [f"{{  // levels [{ss}, {se}), {mode}"]
+        o.append(f"    const int ss = {ss}, se = {se};")
+        first = "ss" if fwd else "se - 1"
+        o.append("    if (ss < se) {")
+        if ring <= 1:
+            # no ring: fronts loaded at their level (first level peeled: the loop itself has
+            # no branch around a load)
+            o.append("        {")
+            o.append(f"            const int k = {first};")
+            o += _indent(self.entry_level(si, sec, None, mode), 12)
+            o.append("        }")
+            if fwd:
+                o.append("        for (int k = ss + 1; k < se; ++k) {")
+            else:
+                o.append("        for (int k = se - 2; k >= ss; --k) {")
+            o += _indent(self.level(si, sec, None, mode), 12)
+            return o + ["        }", "    }", "}"], False
+        pro = []
+        for u in range(ring):
+            for key in keys:
+                fv = self.wvar(*key, self.front[key])
+                pro.append(f"{self.decl_dtype[key[0]].ctype} rg{u}_{fv};")
+                pro += self.load_into(f"rg{u}_{fv}", *key, f"{first} {step} {u} + ({self.front[key]})", maybe_cached=False)
+        o += _indent(self.dup(pro), 8)
+        # first level: reload or continue; ring slot 0
+        o.append("        {")
+        o.append(f"            const int k = {first};")
+        o += _indent(self.entry_level(si, sec, 0, mode) + self.dup(self.refill(0, ring, keys)), 12)
+        o.append("        }")
+        # full blocks of ``ring`` levels: shift only, no branches around loads (a load inside a
+        # branch makes the compiler drain every load in flight at the join)
+        if fwd:
+            o.append("        int kb = ss + 1;")
+            o.append(f"        for (; kb + {ring - 1} < se; kb += {ring}) {{")
+        else:
+            o.append("        int kb = se - 2;")
+            o.append(f"        for (; kb - {ring - 1} >= ss; kb -= {ring}) {{")
+        blocked = self.lblock > 1 and ring % self.lblock == 0 and not self.direct and \
+            _blockable([self.statements(si, sec) for _ in range(2)], self.shift_and_fronts(1 % ring, mode),
+                       {v: key[0] for key, v in self.bases.items()})
+        for g in range(0, ring, self.lblock if blocked else 1):
+            if blocked:
+                o += self._blocked_levels(si, sec, g, ring, mode, keys)
+                continue
+            slot = (g + 1) % ring
+            o.append(f"            {{  // ring slot {slot}")
+            o.append(f"                const int k = kb {step} {g};")
+            o += _indent(self.level(si, sec, slot, mode) + self.dup(self.refill(slot, ring, keys)), 16)
+            o.append("            }")
+        o.append("        }")
+        # the last < ring levels: their fronts are already in the ring
+        for u in range(ring - 1):
+            slot = (u + 1) % ring
+            cond = f"kb + {u} < se" if fwd else f"kb - {u} >= ss"
+            o.append(f"        if ({cond}) {{  // ring slot {slot}")
+            o.append(f"            const int k = kb {step} {u};")
+            o += _indent(self.level(si, sec, slot, mode), 12)
+            o.append("        }")
+        return o + ["    }", "}"], blocked
+
+    def _blocked_levels(self, si, sec, g, ring, mode, keys) -> List[str]:
+        """Tile mode, levels ``kb + g ...`` of a ring block under one LDS barrier: every level's
+        statements before the barrier (the plane writes), one barrier, then every level's
+        statements after it on snapshots of the window values they read."""
+        o = [f"            {{  // levels kb {self.step} {g} .. {g + self.lblock - 1}: one LDS barrier"]
+        posts = []
+        for b in range(self.lblock):
+            u, slot = g + b, (g + b + 1) % ring
+            kv = f"k{b}_"
+            ren = lambda x, kv=kv: _KVAR.sub(kv, x)  # noqa: E731
+            o.append(f"                const int {kv} = kb {self.step} {u};")
+            st = self.statements(si, sec)
+            cut = next(q for q, x in enumerate(st) if x.startswith("gtmi::lds_barrier();"))
+            pre, post = st[:cut], st[cut + 1:]
+            names = sorted(set(_WVAR.findall("\n".join(post))))
+            # pre[0] is the level's k_next update: once for both rows of a thread
+            o += ["                " + ren(x) for x in self.dup(self.shift_and_fronts(slot, mode)) + pre[:1] + self.dup(pre[1:])]
+            o += _indent(self.dup([f"auto sn{b}_{n} = {n};" for n in names]), 16)
+            o += ["                " + ren(x) for x in self.dup(self.refill(slot, ring, keys))]
+            snap = re.compile(r"\b(" + "|".join(map(re.escape, names)) + r")\b") if names else None
+            posts += self.dup([ren(snap.sub(lambda m, b=b: f"sn{b}_{m.group(1)}", x) if snap else x) for x in post])
+        o.append("                gtmi::lds_barrier();  // the block's planes are complete")
+        return o + _indent(posts, 16) + ["            }"]
+
+    def _tail_parts(self) -> Tuple[List[str], List[Tuple[str, str, str]]]:
+        """Split a section of the reading loop by where the tail-cached fronts come from: the
+        declarations of the split points and the (ss, se, mode) segments in sweep order. A front
+        k + fd is cached iff tc0 <= k + fd < tc1. With lo/hi the smallest/largest fd of the tail keys:
+        all fronts cached for k in [tc0 - lo, tc1 - hi), none below tc0 - hi or from
+        tc1 - lo on. Levels before the cached band in sweep order are run "mixed" (their
+        ring would look ahead into the cache); the band itself reads LDS; the levels after
+        it stream from memory with the ring."""
+        fds = [self.front[k_] for k_ in self.tail_keys]
+        lo_fd, hi_fd = min(fds), max(fds)
+        mn = lambda a, b: f"({a} < {b} ? {a} : {b})"  # noqa: E731
+        mx = lambda a, b: f"({a} > {b} ? {a} : {b})"  # noqa: E731
+        decl = [f"        const int x1 = tc0 - ({hi_fd}), x2 = {mx('x1', f'tc0 - ({lo_fd})')};",
+                f"        const int x3 = {mx('x2', f'tc1 - ({hi_fd})')}, x4 = tc1 - ({lo_fd});  // x1 <= x2 <= x3 <= x4"]
+        x1, x2, x3, x4 = "x1", "x2", "x3", "x4"
+        rng_ = lambda a, b: (mx("ks", a) if a else "ks", mn("ke", b) if b else "ke")  # noqa: E731
+        if self.tail.head:
+            # the cache sits at the END of this (reading) sweep: stream the levels before
+            # it with the ring, each side of it the levels whose fronts straddle its edge
+            decl.append("        const int x4b = x4 > x3 ? x4 : x3;")
+            parts = [(*rng_(None, x1), "mem"), (*rng_(x1, x2), "mixed"), (*rng_(x2, x3), "lds"),
+                     (*rng_(x3, "x4b"), "mixed"), (*rng_("x4b", None), "mem")]
+            return decl, parts if self.fwd else parts[::-1]
+        if self.fwd:
+            return decl, [(*rng_(None, x2), "mixed"), (*rng_(x2, x3), "lds"), (*rng_(x3, x4), "mixed"),
+                          (*rng_(x4, None), "mem")]
+        return decl, [(*rng_(x3, None), "mixed"), (*rng_(x2, x3), "lds"), (*rng_(x1, x2), "mixed"),
+                      (*rng_(None, x1), "mem")]
+
+    def section(self, si, sec) -> Tuple[List[str], bool]:
+        lo, hi = interval_bounds(sec.interval)
+        out = [f"    {{  // section {si}", f"        int ks = {lo}, ke = {hi};",
+               "        if (ks < 0) ks = 0; if (ke > nk) ke = nk;"]
+        if self.R:  # the register band's levels run in the unrolled band code
+            out.append("        if (ks < rbase) ks = rbase;" if self.tail.low else "        if (ke > nk - rbase) ke = nk - rbase;")
+        parts = [("ks", "ke", "mem")]
+        if self.tail_keys:
+            decl, parts = self._tail_parts()
+            out += decl
+        blocked = False
+        for ss, se, mode in parts:
+            seg, b = self.segment(si, sec, ss, se, mode)
+            out += _indent(seg, 8)
+            blocked |= b
+        return out + ["    }"], blocked
+
+    def band_k(self, u: int) -> str:
+        return f"{u}" if self.tail.low else f"nk - {self.R} + {u}"
+
+    def prefetch(self, u: int) -> List[str]:
+        """Band level ``u``'s memory fronts into their prefetch registers."""
+        return [f"{self.pfv[(u, key)]} = {self.mem_index(*key, f'({self.band_k(u)}) + ({self.front[key]})')};"
+                for key in self.mem_keys[u]]
+
+    def declare_pf(self, us, indent: str) -> List[str]:
+        return [f"{indent}{self.decl_dtype[key[0]].ctype} {self.pfv[(u, key)]};" for u in us for key in self.mem_keys[u]]
+
+    def band_levels(self, si, sec) -> List[str]:
+        """Section ``si``'s register-band levels: unrolled, static register names. The band
+        is straight-line code, so its memory fronts are software-pipelined explicitly:
+        band level n's fronts are loaded ``kreg_pf`` band levels earlier into registers
+        of their own (a level waiting for its own loads stalls a one-wave-per-SIMD kernel);
+        prefetch distance: see BAND_PF_OVER_RING."""
+        us = [u for u in range(self.R) if self.band_map[u] == si]
+        if not us:
+            return []
+        seq = self.all_us
+        bc = [f"    if (regband) {{  // section {si}: register band levels"]
+        for n_, u in enumerate(sorted(us, reverse=not self.fwd)):
+            pf = {key: self.pfv[(u, key)] for key in self.mem_keys[u]} if self.Pb > 0 else None
+            if n_ == 0:
+                body = (["if (k != k_next) {"] + _indent(self.reload(sec, u, pf), 4) + ["} else {"]
+                        + _indent(self.shift_and_fronts(None, "mem", u, pf), 4) + ["}"])
+            else:
+                body = self.shift_and_fronts(None, "mem", u, pf)
+            g_ = seq.index(u)
+            for t_ in self.issue_at.get(g_, ()):
+                body += self.prefetch(seq[t_])
+            if self.reader_loads is not None and self.Pb > 0:
+                # the reader's band level j is prefetched its own distance (len(reader_loads))
+                # before the reader starts
+                j_ = g_ + len(self.reader_loads) - len(seq)
+                if 0 <= j_ < len(self.reader_loads):
+                    body += ["// the reader's band: prefetched here"] + self.reader_loads[j_]
+            body += self.statements(si, sec, reg=u)
+            bc.append(f"        {{  const int k = {self.band_k(u)};")
+            bc += _indent(body, 12)
+            bc.append("        }")
+        return bc + ["    }"]
+
+    def render(self) -> _LoopText:
+        out = [f"{{  // vertical loop {self.li} ({self.vl.loop_order.name})"]
+        decls = []
+        for (name, di, dj), rng in self.win.items():
+            t = self.decl_dtype[name].ctype
+            for d in range(rng[0], rng[1] + 1):
+                decls.append(f"    {t} {self.wvar(name, di, dj, d)} = ({t})0;")
+        out += self.dup(decls)
+        out.append("    int k_next = -0x7fffffff;")
+        xpf_decls: List[str] = []
+        xpf_loads: List[List[str]] = []
+        if self.R and self.Pb > 0 and self.hands_off:
+            # reader: its first ``pre`` band levels are prefetched by the writer's last band levels
+            xpf_decls = self.declare_pf(self.all_us[:self.pre], "")
+            xpf_loads = [self.prefetch(u) for u in self.all_us[:self.pre]]
+            out += self.declare_pf(self.all_us[self.pre:], "    ")
+        elif self.R and self.Pb > 0:
+            out += self.declare_pf(self.all_us, "    ")
+            out.append("    if (regband) {  // band prefetch prologue (whole band)")
+            for u in self.all_us[:self.pre]:
+                out += _indent(self.prefetch(u), 8)
+            # reader levels the writer's band is too short to reach
+            for j in range(max(0, len(self.reader_loads or ()) - len(self.all_us))):
+                out += _indent(self.reader_loads[j], 8)
+            out.append("    }")
         sec_start = len(out)
         band_code: List[str] = []
-        # register band fronts prefetched across the whole band: one sweep-order list of band
-        # levels over all sections, each level prefetching the one ``Pb`` levels on whatever
-        # section it lies in, and -- for the writer, whose band ends the sweep -- the prologue
-        # issued at the start of the loop, so no band level (nor the first) waits for loads issued
-        # at a section boundary
-        if R:
-            Pb = int(self.opts.get("kreg_pf", self.band_pf_default if self.band_pf_default is not None else P + BAND_PF_OVER_RING))
-            kexpr_of = (lambda u_: f"{u_}") if tail.low else (lambda u_: f"nk - {R} + {u_}")  # noqa: E731
-            all_us = sorted((u for u in range(R) if band_map[u] is not None), reverse=not fwd)
-            mem_keys = {}
-            for u in all_us:
-                mk = []
-                for key in win:
-                    if not front_load[key] or not self._mem(key[0]):
-                        continue
-                    if key[0] in wnames and "K" not in self.st.decl(key[0]).axes:
-                        continue  # as ring_keys: one address for every level, loaded at its level
-                    if key[0] in tail_read and key[1:] == (0, 0) and 0 <= u + front[key] < R:
-                        continue  # served by the register band
-                    mk.append(key)
-                mem_keys[u] = mk
-            pfv = {}
-
-            def prefetch(u_):
-                return [f"{pfv[(u_, key)]} = {mem_index(key[0], key[1], key[2], f'({kexpr_of(u_)}) + ({front[key]})')};"
-                        for key in mem_keys[u_]]
-
-            def declare_pf(us_, indent):
-                d = []
-                for u in us_:
-                    for key in mem_keys[u]:
-                        pfv[(u, key)] = f"bp{u}_{wvar(*key, front[key])}"
-                        d.append(f"{indent}{decl_dtype[key[0]].ctype} {pfv[(u, key)]};")
-                return d
-
-            # span schedule: ``pre`` levels are in flight when the band starts (the prologue, or for
-            # the reader the writer's last levels: at most the default distance, which the writer's
-            # registers afford); the rest are issued at most two per level, each ``Pb`` levels
-            # ahead or as early as that allows, so a deeper distance ramps up within the band
-            issue_at: Dict[int, List[int]] = {}
-            if Pb > 0:
-                pre = Pb
-                if self._xpf and li == tail.b:
-                    pre = min(Pb, int(self.opts.get("kreg_pf", P + BAND_PF_OVER_RING)))
-                pre = min(pre, len(all_us))
-                pend = list(range(pre, len(all_us)))
-                for p_ in range(len(all_us)):
-                    while pend and pend[0] - Pb <= p_ and len(issue_at.get(p_, ())) < 2:
-                        issue_at.setdefault(p_, []).append(pend.pop(0))
-            if Pb > 0 and self._xpf and li == tail.b:
-                # reader: its first ``pre`` band levels are prefetched by the writer's last band levels
-                self._xpf_decls = declare_pf(all_us[:pre], "")
-                self._xpf_loads = [prefetch(u) for u in all_us[:pre]]
-                out += declare_pf(all_us[pre:], "    ")
-                sec_start = len(out)
-            elif Pb > 0:
-                out += declare_pf(all_us, "    ")
-                out.append("    if (regband) {  // band prefetch prologue (whole band)")
-                for u in all_us[:pre]:
-                    out += ["        " + x for x in prefetch(u)]
-                if self._xpf and li == tail.a:  # reader levels the writer's band is too short to reach
-                    for j in range(max(0, len(self._xpf_loads) - len(all_us))):
-                        out += ["        " + x for x in self._xpf_loads[j]]
-                out.append("    }")
-                sec_start = len(out)
-        for si, sec in enumerate(vl.sections):
-            lo, hi = interval_bounds(sec.interval)
-            out.append(f"    {{  // section {si}")
-            out.append(f"        int ks = {lo}, ke = {hi};")
-            out.append("        if (ks < 0) ks = 0; if (ke > nk) ke = nk;")
-            if R:  # the register band's levels run in the unrolled band code
-                out.append("        if (ks < rbase) ks = rbase;" if tail.low else "        if (ke > nk - rbase) ke = nk - rbase;")
-
-            def kaddr(acc: ir.FieldAccess) -> str:
-                kexpr = f"k + ({acc.offset[2]})"
-                if acc.k_offset is not None:
-                    kexpr += f" + (int)({rend(acc.k_offset)})"
-                return kexpr
-
-            def resolve(acc: ir.FieldAccess) -> str:
-                di, dj, dk = acc.offset
-                if acc.name in direct:
-                    return mem_index(acc.name, di, dj, kaddr(acc))
-                if acc.name in self.lds and (di or dj):
-                    return f"lds_{cname(acc.name)}[k & {self.pmask}][ty + ({dj})][tx + ({di})]"
-                return wvar(acc.name, di, dj, dk)
-
-            rend = ExprRenderer(resolve, lambda n: f"s_{cname(n)}", lambda ax: ["i", "j", "k"][ax])
-            rend.exact_fma = bool(int(self.opts.get("exact_fma", 1)))
-            self._kaddr = kaddr
-
-            def shift_and_fronts(slot: Optional[int], mode: str, reg_u: Optional[int] = None,
-                                 pf: Optional[Dict] = None) -> List[str]:
-                """Shift every window one level and load each front: from ring ``slot``, from the
-                LDS tail cache (``mode`` "lds"), from the register band (``reg_u``: the level's band
-                index), from a band prefetch register (``pf``: key -> variable) or from memory here
-                (``slot`` None)."""
-                body = []
-                for key, rng in win.items():
-                    name, di, dj = key
-                    ds = list(range(rng[0], rng[1] + 1))
-                    if fwd:
-                        for d in ds[:-1]:
-                            body.append(f"{wvar(name, di, dj, d)} = {wvar(name, di, dj, d + 1)};")
-                    else:
-                        for d in reversed(ds[1:]):
-                            body.append(f"{wvar(name, di, dj, d)} = {wvar(name, di, dj, d - 1)};")
-                    if front_load[key]:
-                        fd = front[key]
-                        fv = wvar(name, di, dj, fd)
-                        if pf is not None and key in pf:
-                            body.append(f"{fv} = {pf[key]};")
-                        elif reg_u is not None:
-                            body += load_into(fv, name, di, dj, f"k + ({fd})", maybe_cached=False, reg=reg_u + fd)
-                        elif mode == "lds" and key in tail_keys:
-                            body.append(f"{fv} = {tail.var(name)}[(k + ({fd}) - tc0) * 256 + tid];")
-                        elif slot is not None and key in ring_keys:
-                            body.append(f"{fv} = rg{slot}_{fv};")
-                        else:
-                            body += load_into(fv, name, di, dj, f"k + ({fd})", maybe_cached=(mode == "mixed"))
-                return body
-
-            def reload(reg_u: Optional[int] = None, pf: Optional[Dict] = None) -> List[str]:
-                body = []
-                for (name, di, dj), rng in win.items():
-                    if not self._mem(name):
-                        continue
-                    for d in range(rng[0], rng[1] + 1):
-                        if d == 0 and not zero_needed_in(name, di, dj, sec):
-                            continue
-                        if pf is not None and (name, di, dj) in pf and d == front[(name, di, dj)]:
-                            body.append(f"{wvar(name, di, dj, d)} = {pf[(name, di, dj)]};")  # prefetched
-                            continue
-                        body += load_into(wvar(name, di, dj, d), name, di, dj, f"k + ({d})",
-                                          reg=None if reg_u is None else reg_u + d)
-                return body
-
-            def statements() -> List[str]:
-                body = [f"k_next = k {step} 1;"]
-                pending: Set[str] = set()  # LDS planes written since the last barrier (tile mode)
-                for ti, s in enumerate(sec.body):
-                    if self.lds:
-                        reads = {a.name for a, w in iter_accesses([s])
-                                 if not w and isinstance(a, ir.FieldAccess) and a.name in self.lds
-                                 and (a.offset[0] or a.offset[1])}
-                        if reads & pending:
-                            body.append("gtmi::lds_barrier();  // the level's planes are complete")
-                            pending.clear()
-                    code = self._stmt(s, rend, wvar, mem_store)
-                    g = self._guard(li, si, ti)
-                    if self.tile and any(w and self._mem(a.name) and a.name not in self.api
-                                         for a, w in iter_accesses([s])):
-                        g = f"{g} && {self._tile_local(li, si, ti)}" if g else self._tile_local(li, si, ti)
-                    if g:
-                        code = [f"if ({g}) {{"] + ["    " + x for x in code] + ["}"]
-                    body += code
-                    if self.lds:
-                        pending |= {a.name for a, w in iter_accesses([s]) if w and a.name in self.lds}
-                if pending:
-                    # planes written but not read across columns at this level: the next write of
-                    # the same buffer (two levels on) must not overtake a slow reader
-                    body.append("gtmi::lds_barrier();")
-                if tail_write and band_now[0] == "reg":
-                    body.append("// register band: this level's final values")
-                    body += [f"rb_{cname(n)}_{reg_now[0]} = {wvar(n, 0, 0, 0)};" for n in tail_write]
-                elif tail_write and band_now[0] is not False:
-                    stores = [f"{tail.var(n)}[(k - tc0) * 256 + tid] = {wvar(n, 0, 0, 0)};" for n in tail_write]
-                    if band_now[0] is True:
-                        body.append("// LDS tail cache: this level's final values")
-                        body += stores
-                    else:
-                        body.append("if (k >= tc0 && k < tc1) {  // LDS tail cache: this level's final values")
-                        body += ["    " + x for x in stores]
-                        body.append("}")
-                return body
-
-            def entry_level(slot, mode) -> List[str]:
-                """A segment's first level, which may follow a gap: full window reload unless it
-                continues the sweep (the only level with loads inside a branch)."""
-                return (["if (k != k_next) {  // (re)load the full K-window"] + ["    " + x for x in dup(reload())]
-                        + ["} else {"] + ["    " + x for x in dup(shift_and_fronts(slot, mode))] + ["}"]
-                        + merged(statements()))
-
-            def refill(slot, R, keys) -> List[str]:
-                body = []
-                for key in keys:
-                    fv = wvar(*key, front[key])
-                    body += load_into(f"rg{slot}_{fv}", *key, f"k {step} {R} + ({front[key]})", maybe_cached=False)
-                return body
-
-            def segment(ss, se, mode: str) -> List[str]:
-                """Levels [ss, se) of the section in sweep order. ``mode``: "mem" (no front of
-                these levels is tail-cached), "lds" (every tail-cached front is), "mixed"."""
-                keys = [k_ for k_ in ring_keys if not (mode == "lds" and k_ in tail_keys)] if mode != "mixed" else []
-                R = _section_ring(sec.interval, P) if keys else 0
-                o = [f"{{  // levels [{ss}, {se}), {mode}"]
-                o.append(f"    const int ss = {ss}, se = {se};")
-                first = "ss" if fwd else "se - 1"
-                o.append("    if (ss < se) {")
-                if R <= 1:
-                    # no ring: fronts loaded at their level (first level peeled: the loop itself has
-                    # no branch around a load)
-                    o.append("        {")
-                    o.append(f"            const int k = {first};")
-                    o += ["            " + x for x in entry_level(None, mode)]
-                    o.append("        }")
-                    if fwd:
-                        o.append("        for (int k = ss + 1; k < se; ++k) {")
-                    else:
-                        o.append("        for (int k = se - 2; k >= ss; --k) {")
-                    o += ["            " + x for x in dup(shift_and_fronts(None, mode)) + merged(statements())]
-                    o.append("        }")
-                    o.append("    }")
-                    o.append("}")
-                    return o
-                pro = []
-                for u in range(R):
-                    for key in keys:
-                        fv = wvar(*key, front[key])
-                        t = decl_dtype[key[0]].ctype
-                        pro.append(f"{t} rg{u}_{fv};")
-                        pro += load_into(f"rg{u}_{fv}", *key, f"{first} {step} {u} + ({front[key]})", maybe_cached=False)
-                o += ["        " + x for x in dup(pro)]
-                # first level: reload or continue; ring slot 0
-                o.append("        {")
-                o.append(f"            const int k = {first};")
-                o += ["            " + x for x in entry_level(0, mode)]
-                o += ["            " + x for x in dup(refill(0, R, keys))]
-                o.append("        }")
-                # full blocks of R levels: shift only, no branches around loads (a load inside a
-                # branch makes the compiler drain every load in flight at the join)
-                if fwd:
-                    o.append("        int kb = ss + 1;")
-                    o.append(f"        for (; kb + {R - 1} < se; kb += {R}) {{")
-                else:
-                    o.append("        int kb = se - 2;")
-                    o.append(f"        for (; kb - {R - 1} >= ss; kb -= {R}) {{")
-                blocked = self.lblock > 1 and R % self.lblock == 0 and not direct and \
-                    self._blockable([statements() for _ in range(2)], shift_and_fronts(1 % R, mode),
-                                    self._base_fields())
-                self._blocked_any |= blocked
-                for g in range(0, R, self.lblock if blocked else 1):
-                    if not blocked:
-                        u, slot = g, (g + 1) % R
-                        o.append(f"            {{  // ring slot {slot}")
-                        o.append(f"                const int k = kb {step} {u};")
-                        o += ["                " + x for x in dup(shift_and_fronts(slot, mode)) + merged(statements())
-                              + dup(refill(slot, R, keys))]
-                        o.append("            }")
-                        continue
-                    # tile mode, several levels per LDS barrier: every level's statements before
-                    # the barrier (the plane writes), one barrier, then every level's statements
-                    # after it on snapshots of the window values they read
-                    o.append(f"            {{  // levels kb {step} {g} .. {g + self.lblock - 1}: one LDS barrier")
-                    posts = []
-                    for b in range(self.lblock):
-                        u, slot = g + b, (g + b + 1) % R
-                        kv = f"k{b}_"
-                        ren = lambda x, kv=kv: _KVAR.sub(kv, x)  # noqa: E731
-                        o.append(f"                const int {kv} = kb {step} {u};")
-                        st = statements()
-                        cut = next(q for q, x in enumerate(st) if x.startswith("gtmi::lds_barrier();"))
-                        pre, post = st[:cut], st[cut + 1:]
-                        names = sorted(set(_WVAR.findall("\n".join(post))))
-                        # pre[0] is the level's k_next update: once for both rows of a thread
-                        o += ["                " + ren(x) for x in dup(shift_and_fronts(slot, mode)) + pre[:1] + dup(pre[1:])]
-                        o += ["                " + x for x in dup([f"auto sn{b}_{n} = {n};" for n in names])]
-                        o += ["                " + ren(x) for x in dup(refill(slot, R, keys))]
-                        snap = re.compile(r"\b(" + "|".join(map(re.escape, names)) + r")\b") if names else None
-                        posts += dup([ren(snap.sub(lambda m, b=b: f"sn{b}_{m.group(1)}", x) if snap else x) for x in post])
-                    o.append("                gtmi::lds_barrier();  // the block's planes are complete")
-                    o += ["                " + x for x in posts]
-                    o.append("            }")
-                o.append("        }")
-                # the last < R levels: their fronts are already in the ring
-                for u in range(R - 1):
-                    slot = (u + 1) % R
-                    cond = f"kb + {u} < se" if fwd else f"kb - {u} >= ss"
-                    o.append(f"        if ({cond}) {{  // ring slot {slot}")
-                    o.append(f"            const int k = kb {step} {u};")
-                    o += ["            " + x for x in dup(shift_and_fronts(slot, mode)) + merged(statements())]
-                    o.append("        }")
-                o.append("    }")
-                o.append("}")
-                return o
-
-            if tail_keys:
-                # split the section by where the tail-cached fronts come from. A front k + fd is
-                # cached iff tc0 <= k + fd < tc1. With lo/hi the smallest/largest fd of the tail keys:
-                # all fronts cached for k in [tc0 - lo, tc1 - hi), none below tc0 - hi or from
-                # tc1 - lo on. Levels before the cached band in sweep order are run "mixed" (their
-                # ring would look ahead into the cache); the band itself reads LDS; the levels after
-                # it stream from memory with the ring.
-                fds = [front[k_] for k_ in tail_keys]
-                lo_fd, hi_fd = min(fds), max(fds)
-                mn = lambda a, b: f"({a} < {b} ? {a} : {b})"  # noqa: E731
-                mx = lambda a, b: f"({a} > {b} ? {a} : {b})"  # noqa: E731
-                out.append(f"        const int x1 = tc0 - ({hi_fd}), x2 = {mx('x1', f'tc0 - ({lo_fd})')};")
-                out.append(f"        const int x3 = {mx('x2', f'tc1 - ({hi_fd})')}, x4 = tc1 - ({lo_fd});  // x1 <= x2 <= x3 <= x4")
-                x1, x2, x3, x4 = "x1", "x2", "x3", "x4"
-                rng_ = lambda a, b: (mx("ks", a) if a else "ks", mn("ke", b) if b else "ke")  # noqa: E731
-                if tail.head:
-                    # the cache sits at the END of this (reading) sweep: stream the levels before
-                    # it with the ring, each side of it the levels whose fronts straddle its edge
-                    out.append("        const int x4b = x4 > x3 ? x4 : x3;")
-                    if fwd:
-                        parts = [(*rng_(None, x1), "mem"), (*rng_(x1, x2), "mixed"), (*rng_(x2, x3), "lds"),
-                                 (*rng_(x3, "x4b"), "mixed"), (*rng_("x4b", None), "mem")]
-                    else:
-                        parts = [(*rng_("x4b", None), "mem"), (*rng_(x3, "x4b"), "mixed"), (*rng_(x2, x3), "lds"),
-                                 (*rng_(x1, x2), "mixed"), (*rng_(None, x1), "mem")]
-                elif fwd:
-                    parts = [(*rng_(None, x2), "mixed"), (*rng_(x2, x3), "lds"), (*rng_(x3, x4), "mixed"),
-                             (*rng_(x4, None), "mem")]
-                else:
-                    parts = [(*rng_(x3, None), "mixed"), (*rng_(x2, x3), "lds"), (*rng_(x1, x2), "mixed"),
-                             (*rng_(None, x1), "mem")]
-                for ss, se, mode in parts:
-                    out += ["        " + x for x in segment(ss, se, mode)]
-            else:
-                out += ["        " + x for x in segment("ks", "ke", "mem")]
-            out.append("    }")
-            us = [u for u in range(R) if band_map[u] == si] if R else []
-            if us:
-                # this section's register-band levels: unrolled, static register names. The band
-                # is straight-line code, so its memory fronts are software-pipelined explicitly:
-                # band level n's fronts are loaded ``kreg_pf`` band levels earlier into registers
-                # of their own (a level waiting for its own loads stalls a one-wave-per-SIMD kernel)
-                order_us = sorted(us, reverse=not fwd)
-                # prefetch distance: see BAND_PF_OVER_RING
-                bc = [f"    if (regband) {{  // section {si}: register band levels"]
-                seq = all_us
-                for n_, u in enumerate(order_us):
-                    kexpr = kexpr_of(u)
-                    reg_now[0], band_now[0] = u, "reg"
-                    pf = {key: pfv[(u, key)] for key in mem_keys[u]} if Pb > 0 else None
-                    if n_ == 0:
-                        body = (["if (k != k_next) {"] + ["    " + x for x in reload(u, pf)] + ["} else {"]
-                                + ["    " + x for x in shift_and_fronts(None, "mem", u, pf)] + ["}"])
-                    else:
-                        body = shift_and_fronts(None, "mem", u, pf)
-                    g_ = seq.index(u)
-                    for t_ in issue_at.get(g_, ()):
-                        body += prefetch(seq[t_])
-                    if self._xpf and li == tail.a and Pb > 0:
-                        # the reader's band level j is prefetched its own distance (len(_xpf_loads))
-                        # before the reader starts
-                        j_ = g_ + len(self._xpf_loads) - len(seq)
-                        if 0 <= j_ < len(self._xpf_loads):
-                            body += ["// the reader's band: prefetched here"] + self._xpf_loads[j_]
-                    body += statements()
-                    reg_now[0], band_now[0] = None, None
-                    bc.append(f"        {{  const int k = {kexpr};")
-                    bc += ["            " + x for x in body]
-                    bc.append("        }")
-                bc.append("    }")
-                band_code += bc
+        blocked = False
+        for si, sec in enumerate(self.vl.sections):
+            lines, b = self.section(si, sec)
+            out += lines
+            blocked |= b
+            if self.R:
+                band_code += self.band_levels(si, sec)
         if band_code:
-            if (li == tail.a) != tail.head:
+            if (self.li == self.tail.a) != self.tail.head:
                 out += band_code  # the band ends the writer's sweep (tail) or the reader's (head)
             else:
                 out[sec_start:sec_start] = band_code  # and starts the other one
-        out.append("}")
-        return out
-
-    def _stmt(self, s, rend, wvar, mem_store) -> List[str]:
-        if isinstance(s, ir.Assign):
-            name = s.target.name
-            if name in self.direct:
-                st = mem_store(name, self._kaddr(s.target), rend(s.value))
-                if name in self.api and self.tile:
-                    st = f"if (own) {st}"
-                elif name in self.api and any(self.ext):
-                    st = f"if (i >= 0 && i < p.ni && j >= 0 && j < p.nj) {st}"
-                return [st]
-            tgt = wvar(name, 0, 0, 0)
-            out = [f"{tgt} = {rend(s.value)};"]
-            if name in self.lds:
-                out.append(f"lds_{cname(name)}[k & {self.pmask}][ty][tx] = {tgt};")
-            if self._mem(name):
-                st = mem_store(name, "k", tgt)
-                if name in self.api and self.tile:
-                    st = f"if (own) {st}"  # overlapping tiles: each output column has one owner
-                elif name in self.api and any(self.ext):
-                    st = f"if (i >= 0 && i < p.ni && j >= 0 && j < p.nj) {st}"
-                out.append(st)
-            return out
-        if isinstance(s, ir.If):
-            out = [f"if ({rend(s.cond)}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, wvar, mem_store)]
-            if s.orelse:
-                out.append("} else {")
-                for x in s.orelse:
-                    out += ["    " + y for y in self._stmt(x, rend, wvar, mem_store)]
-            out.append("}")
-            return out
-        if isinstance(s, ir.While):
-            out = [f"while ({rend(s.cond)}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, wvar, mem_store)]
-            out.append("}")
-            return out
-        if isinstance(s, ir.HorizontalRegion):
-            cond = region_condition(s.masks, "i", "j", "p.ni", "p.nj")
-            out = [f"if ({cond}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, wvar, mem_store)]
-            out.append("}")
-            return out
-        raise TypeError(type(s))
-
-
-def _bound_eq(a: ir.AxisBound, b: ir.AxisBound) -> bool:
-    return a.level == b.level and a.offset == b.offset
-
-
-_contiguous = sections_contiguous
+        return _LoopText(out + ["}"], blocked, xpf_decls, xpf_loads)
 
 
 def _covers_all_levels(vl: ir.VerticalLoop, fwd: bool) -> bool:
     """The loop's sections run every level of [0, nk) exactly once (statically provable)."""
-    if not vl.sections or not _contiguous(vl):
+    if not vl.sections or not sections_contiguous(vl):
         return False
     first, last = vl.sections[0].interval, vl.sections[-1].interval
     lo = first.start if fwd else last.start
     hi = last.end if fwd else first.end
-    return _bound_eq(lo, ir.AxisBound(ir.LevelMarker.START, 0)) and _bound_eq(hi, ir.AxisBound(ir.LevelMarker.END, 0))
+    return lo == ir.AxisBound(ir.LevelMarker.START, 0) and hi == ir.AxisBound(ir.LevelMarker.END, 0)
 
 
 def _ge(level, bound: ir.AxisBound) -> bool:

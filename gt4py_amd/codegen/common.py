@@ -1,17 +1,17 @@
 """Shared pieces of the gt:mi355x HIP code generators: C names and literals, the typed-IR
 expression renderer (numpy-faithful casts and native functions), the field-argument model
-(``FieldSlot`` -> kernel parameters / host packing) and launch constants."""
+(``FieldSlot`` -> kernel parameter struct / host packing), the XCD block remap, the statement
+walker for ``if``/``while``/horizontal regions, and launch constants."""
 
 from __future__ import annotations
 
 import dataclasses
 import math
-from typing import Dict, List, Optional, Set, Tuple
+from typing import List, Set, Tuple
 
 from gt4py_amd import ir
-from gt4py_amd.codegen.plan import ColumnKernel, KernelPlan, PlaneKernel, UnsupportedStencil
+from gt4py_amd.codegen.plan import UnsupportedStencil
 from gt4py_amd.ir import DataType
-from gt4py_amd.passes import ZERO_EXTENT, StencilAnalysis, iter_accesses
 
 WAVE = 64
 PLANE_BLOCK_WAVES = 4
@@ -280,8 +280,49 @@ def interval_bounds(itv: ir.Interval) -> Tuple[str, str]:
     return b(itv.start), b(itv.end)
 
 
-# ------------------------------------------------------------------------------------------
-# K1: J-streaming plane kernel
+def params_struct(kid: int, used: List[FieldSlot], written: Set[str], scalars, extra: List[str]) -> List[str]:
+    """``struct K<kid>Params``: the used field slots, the scalars, then the generator's own members."""
+    L = [f"struct K{kid}Params {{"]
+    for s in used:
+        L += ["    " + x for x in kparam_decl(s, s.name in written)]
+    L += [f"    {s.dtype.ctype} s_{cname(s.name)};" for s in scalars]
+    return L + ["    " + x for x in extra] + ["};", ""]
+
+
+def host_params(kid: int, used: List[FieldSlot], written: Set[str], scalars) -> List[str]:
+    """Host side: ``K<kid>Params p`` with its field members filled and its scalars copied."""
+    H = [f"K{kid}Params p;"]
+    for s in used:
+        H += host_fill(s, "p", s.name in written)
+    return H + [f"memcpy(&p.s_{cname(s.name)}, &sc[{i}], sizeof(p.s_{cname(s.name)}));" for i, s in enumerate(scalars)]
+
+
+def xcd_remap(w: str) -> List[str]:
+    """Block ``b`` of ``nb`` -> work item ``w``: consecutive work items run on one XCD (8 XCDs,
+    blocks dispatched round-robin over them)."""
+    return [
+        "const int q = nb >> 3, r = nb & 7, xcd = b & 7, slot = b >> 3;",
+        f"const int {w} = (xcd < r) ? xcd * (q + 1) + slot : r * (q + 1) + (xcd - r) * q + slot;",
+    ]
+
+
+def render_stmt(s, rend, leaf, iv: str, jv: str) -> List[str]:
+    """C++ of a statement: the ``If``/``While``/``HorizontalRegion`` nesting here, every other
+    statement by ``leaf(s)``; ``iv``/``jv`` are the I and J index expressions of the regions."""
+    def block(body):
+        return ["    " + y for x in body for y in render_stmt(x, rend, leaf, iv, jv)]
+
+    if isinstance(s, ir.If):
+        out = [f"if ({rend(s.cond)}) {{"] + block(s.body)
+        if s.orelse:
+            out += ["} else {"] + block(s.orelse)
+        return out + ["}"]
+    if isinstance(s, ir.While):
+        return [f"while ({rend(s.cond)}) {{"] + block(s.body) + ["}"]
+    if isinstance(s, ir.HorizontalRegion):
+        return [f"if ({region_condition(s.masks, iv, jv, 'p.ni', 'p.nj')}) {{"] + block(s.body) + ["}"]
+    return leaf(s)
+
 
 def region_condition(masks, iv, jv, ni, nj) -> str:
     def bound(b, n):

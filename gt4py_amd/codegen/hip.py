@@ -28,19 +28,14 @@ numpy backend for + - * / comparisons and selects.
 
 from __future__ import annotations
 
-import dataclasses
-import math
-from typing import Dict, List, Optional, Set, Tuple
+import json
+from typing import Dict, Tuple
 
 from gt4py_amd import ir
-from gt4py_amd.codegen.plan import ColumnKernel, KernelPlan, PlaneKernel, UnsupportedStencil
-from gt4py_amd.ir import DataType
-from gt4py_amd.passes import ZERO_EXTENT, StencilAnalysis, iter_accesses
+from gt4py_amd.codegen.plan import KernelPlan, PlaneKernel
+from gt4py_amd.passes import StencilAnalysis
 from gt4py_amd.codegen.column import ColumnGen
-from gt4py_amd.codegen.common import (  # noqa: F401  (re-exported)
-    COLUMN_BLOCK, PLANE_BLOCK_WAVES, PLANE_MIN_JCHUNK, PLANE_TARGET_BLOCKS, WAVE, ExprRenderer, FieldSlot, cname,
-    host_fill, interval_bounds, kparam_decl, literal, region_condition,
-)
+from gt4py_amd.codegen.common import ExprRenderer, FieldSlot, cname
 from gt4py_amd.codegen.plane import PlaneGen
 
 # ------------------------------------------------------------------------------------------
@@ -58,6 +53,36 @@ def jsplit_native(analysis: StencilAnalysis, plan: KernelPlan) -> bool:
     return not any(
         isinstance(n, ir.HorizontalRegion) for vl in st.vertical_loops for sec in vl.sections for n in ir.walk(sec.body)
     )
+
+
+def stencil_signature(st, plan: KernelPlan, abi_fields, components) -> Dict:
+    """The library's self-description (``gtmi_stencil_signature``): ABI fields, scratch buffers,
+    scalars (and whether any statement or component index uses them), kernel kinds."""
+    used_scalars = {
+        n.name for vl in st.vertical_loops for sec in vl.sections for n in ir.walk(sec.body) if isinstance(n, ir.ScalarAccess)
+    }
+    for comp in components.values():
+        used_scalars |= {n.name for x in comp.index for n in ir.walk(x) if isinstance(n, ir.ScalarAccess)}
+    return {
+        "abi": 3,
+        "fields": [
+            {"name": p.name, "dtype": p.dtype.name.lower(), "axes": list(p.axes), "data_dims": list(p.data_dims)}
+            for p in abi_fields
+        ],
+        "scratch": [
+            {
+                "name": t,
+                "dtype": st.decl(t).dtype.name.lower(),
+                "extent": [list(e) for e in plan.scratch_extent[t]],
+                "axes": list(st.decl(t).axes),
+            }
+            for t in plan.scratch
+        ],
+        "scalars": [
+            {"name": s.name, "dtype": s.dtype.name.lower(), "used": s.name in used_scalars} for s in st.scalar_params()
+        ],
+        "kernels": [type(k).__name__ for k in plan.kernels],
+    }
 
 
 def generate(
@@ -90,33 +115,7 @@ def generate(
             ks, hs = ColumnGen(analysis, plan, k, slots, kid, opts).render()
         kernels_src.append(ks)
         launches.append(hs)
-    import json
-
-    used_scalars = {
-        n.name for vl in st.vertical_loops for sec in vl.sections for n in ir.walk(sec.body) if isinstance(n, ir.ScalarAccess)
-    }
-    for comp in components.values():
-        used_scalars |= {n.name for x in comp.index for n in ir.walk(x) if isinstance(n, ir.ScalarAccess)}
-    signature = {
-        "abi": 3,
-        "fields": [
-            {"name": p.name, "dtype": p.dtype.name.lower(), "axes": list(p.axes), "data_dims": list(p.data_dims)}
-            for p in abi_fields
-        ],
-        "scratch": [
-            {
-                "name": t,
-                "dtype": st.decl(t).dtype.name.lower(),
-                "extent": [list(e) for e in plan.scratch_extent[t]],
-                "axes": list(st.decl(t).axes),
-            }
-            for t in plan.scratch
-        ],
-        "scalars": [
-            {"name": s.name, "dtype": s.dtype.name.lower(), "used": s.name in used_scalars} for s in st.scalar_params()
-        ],
-        "kernels": [type(k).__name__ for k in plan.kernels],
-    }
+    signature = stencil_signature(st, plan, abi_fields, components)
     sig_json = json.dumps(signature).replace("\\", "\\\\").replace('"', '\\"')
     roctx_name = "gtmi:" + "".join(c if (c.isalnum() or c in "._-") else "_" for c in st.name)
     n_scalars = len(st.scalar_params())

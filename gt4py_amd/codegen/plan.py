@@ -113,6 +113,16 @@ def _tile_lds_names(vl: ir.VerticalLoop) -> Optional[List[str]]:
     return names
 
 
+def _read_ij_of_written(accesses) -> Optional[ir.FieldAccess]:
+    """The first read, at an IJ offset, of a name that ``accesses`` also write (None: there is none)."""
+    accs = list(accesses)
+    written = {acc.name for acc, w in accs if w}
+    for acc, w in accs:
+        if not w and isinstance(acc, ir.FieldAccess) and acc.name in written and (acc.offset[0] or acc.offset[1]):
+            return acc
+    return None
+
+
 def make_plan(analysis: StencilAnalysis, column_only: bool = False, pointwise_plane: bool = False,
               tile: bool = False) -> KernelPlan:
     """``column_only``: every computation runs in column kernels (the staged fallback, after
@@ -121,7 +131,6 @@ def make_plan(analysis: StencilAnalysis, column_only: bool = False, pointwise_pl
     IJ offsets (same level) becomes a tile-mode column kernel instead of being rejected."""
     st = analysis.stencil
     temps = {t.name for t in st.temporaries}
-    api = {p.name for p in st.field_params()}
 
     kernels: List[object] = []
     run: List[int] = []
@@ -154,21 +163,12 @@ def make_plan(analysis: StencilAnalysis, column_only: bool = False, pointwise_pl
                 continue
             if vl.loop_order != ir.LoopOrder.PARALLEL:
                 # sequential loops: values produced in the loop may not be read at IJ offsets
-                written = set()
-                for acc, w in _loop_accesses(vl):
-                    if w:
-                        written.add(acc.name)
-                for acc, w in _loop_accesses(vl):
-                    if (
-                        not w
-                        and isinstance(acc, ir.FieldAccess)
-                        and acc.name in written
-                        and (acc.offset[0] or acc.offset[1])
-                    ):
-                        raise UnsupportedStencil(
-                            f"'{acc.name}' is written in a {vl.loop_order.name} loop and read at a horizontal "
-                            f"offset {acc.offset[:2]} in the same loop"
-                        )
+                acc = _read_ij_of_written(_loop_accesses(vl))
+                if acc is not None:
+                    raise UnsupportedStencil(
+                        f"'{acc.name}' is written in a {vl.loop_order.name} loop and read at a horizontal "
+                        f"offset {acc.offset[:2]} in the same loop"
+                    )
             # a column kernel may not consume values at IJ offsets produced earlier in the same run
             # (RAW across columns), nor overwrite values an earlier loop of the run read at IJ
             # offsets (WAR across columns): either needs a grid-wide barrier -> new kernel
@@ -235,22 +235,9 @@ def make_plan(analysis: StencilAnalysis, column_only: bool = False, pointwise_pl
     # column kernels must not read scratch temporaries written inside the same kernel at IJ offsets
     for k in kernels:
         if isinstance(k, ColumnKernel) and not k.tile:
-            written = set()
-            for li in k.loops:
-                for acc, w in _loop_accesses(st.vertical_loops[li]):
-                    if w:
-                        written.add(acc.name)
-            for li in k.loops:
-                for acc, w in _loop_accesses(st.vertical_loops[li]):
-                    if (
-                        not w
-                        and isinstance(acc, ir.FieldAccess)
-                        and acc.name in written
-                        and (acc.offset[0] or acc.offset[1])
-                    ):
-                        raise UnsupportedStencil(
-                            f"'{acc.name}' is produced and read at an IJ offset inside one column kernel"
-                        )
+            acc = _read_ij_of_written(x for li in k.loops for x in _loop_accesses(st.vertical_loops[li]))
+            if acc is not None:
+                raise UnsupportedStencil(f"'{acc.name}' is produced and read at an IJ offset inside one column kernel")
     # PARALLEL plane kernels: K offsets only on values not written in the same section
     for k in kernels:
         if isinstance(k, PlaneKernel):
@@ -265,5 +252,4 @@ def make_plan(analysis: StencilAnalysis, column_only: bool = False, pointwise_pl
                         f"'{acc.name}' is written in a PARALLEL section and read at a K offset in the same section"
                     )
     scratch_extent = {t: analysis.extents.fields.get(t, ZERO_EXTENT) for t in scratch}
-    del api
     return KernelPlan(kernels, scratch, scratch_extent)

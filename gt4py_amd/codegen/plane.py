@@ -6,19 +6,41 @@ See ``codegen/hip.py`` for the skeleton's description and DESIGN.md §3.
 from __future__ import annotations
 
 import dataclasses
-import math
 from typing import Dict, List, Optional, Set, Tuple
 
 from gt4py_amd import ir
-from gt4py_amd.codegen.plan import ColumnKernel, KernelPlan, PlaneKernel, UnsupportedStencil
+from gt4py_amd.codegen.plan import KernelPlan, PlaneKernel, UnsupportedStencil
 from gt4py_amd.ir import DataType
-from gt4py_amd.passes import ZERO_EXTENT, StencilAnalysis, iter_accesses
-from gt4py_amd.codegen.common import (  # noqa: F401
-    COLUMN_BLOCK, PLANE_BLOCK_WAVES, PLANE_LVLSYNC_MAX_LEVELS, PLANE_LVLSYNC_MAX_PLANE, PLANE_MIN_JCHUNK, PLANE_ORDER_AUTO, PLANE_TARGET_BLOCKS, WAVE, ExprRenderer, FieldSlot, cname,
-    host_fill, interval_bounds, kparam_decl, literal, region_condition,
+from gt4py_amd.passes import StencilAnalysis, iter_accesses
+from gt4py_amd.codegen.common import (
+    PLANE_BLOCK_WAVES, PLANE_LVLSYNC_MAX_LEVELS, PLANE_LVLSYNC_MAX_PLANE, PLANE_MIN_JCHUNK, PLANE_ORDER_AUTO,
+    PLANE_TARGET_BLOCKS, WAVE, ExprRenderer, FieldSlot, cname, host_params, interval_bounds, params_struct, render_stmt,
+    xcd_remap,
 )
 
-# ------------------------------------------------------------------------------------------
+
+@dataclasses.dataclass(frozen=True)
+class PlaneOptions:
+    """The backend options the plane generator reads, parsed once (None: the default depends on
+    the kernel, see where it is used)."""
+
+    order: int = PLANE_ORDER_AUTO
+    nt_load: int = 1  # 2: every load non-temporal (experiment)
+    nt_store: int = 1
+    dpp: int = 1  # DPP wave rotate for +-1 lanes (gtmi_device.h)
+    jmirror: int = 1
+    jchunk: int = 0
+    min_blocks: int = 0  # blocks per CU the register budget must allow
+    row_unroll: int = -1
+    bufld: int = -1
+    exact_fma: int = 1
+    vector: Optional[int] = None
+    prefetch: Optional[int] = None
+    strip_align: Optional[int] = None
+
+    @classmethod
+    def parse(cls, opts) -> "PlaneOptions":
+        return cls(**{f.name: int(opts[f.name]) for f in dataclasses.fields(cls) if f.name in opts})
 
 
 @dataclasses.dataclass
@@ -89,6 +111,7 @@ class PlaneGen:
         self.slots: Dict[str, FieldSlot] = slots
         self.kid = kid
         self.opts = opts
+        self.o = PlaneOptions.parse(opts)
         self.vl = self.st.vertical_loops[kernel.loop]
         self.sec = self.vl.sections[kernel.section]
         for acc, w in iter_accesses(self.sec.body):
@@ -250,7 +273,7 @@ class PlaneGen:
         self.w_out = self.npos - h_lo - h_hi
         # align output strips to 128-B lines of the widest stored field (measured: +5-10% on MI355X)
         stored = [self.st.decl(n).dtype.itemsize for n in self.current if self._mem_backed(n)]
-        align = int(self.opts.get("strip_align", 128 // max(stored) if stored else 0))
+        align = self.o.strip_align if self.o.strip_align is not None else (128 // max(stored) if stored else 0)
         if align > 1 and self.w_out >= 2 * align:
             self.w_out = (self.w_out // align) * align
         if self.w_out < 8:
@@ -264,10 +287,8 @@ class PlaneGen:
 
     def _nt_load(self, v: Val) -> bool:
         """Non-temporal loads for streams read once (no IJ offsets), if enabled."""
-        if not self.opts.get("nt_load", 1):
-            return False
-        if int(self.opts.get("nt_load", 1)) == 2:  # experiment: every load non-temporal
-            return True
+        if self.o.nt_load in (0, 2):
+            return self.o.nt_load == 2
         return v.needed_ilo == 0 and v.needed_ihi == 0 and v.depth == 1
 
     def _lane_range(self, v: Val) -> Tuple[int, int]:
@@ -280,8 +301,8 @@ class PlaneGen:
     def render(self) -> Tuple[str, str]:
         self.build()
         variants = [1]
-        if "vector" in self.opts:
-            vec = int(self.opts["vector"])
+        if self.o.vector is not None:
+            vec = self.o.vector
         else:  # 16 B per lane for the widest memory-backed type of the section
             sizes = [self.st.decl(n).dtype.itemsize for (n, _dk) in self.loads] + [
                 self.st.decl(n).dtype.itemsize for n in self.current if self._mem_backed(n)
@@ -312,7 +333,7 @@ class PlaneGen:
         end of their sweep -- so the second read hits the XCD's L2 instead of HBM. Chunks of one
         level are consecutive work items on one XCD (XCD-aware order), i.e. they run together.
         """
-        if not int(self.opts.get("jmirror", 1)) or self.mirror:
+        if not self.o.jmirror or self.mirror:
             return False
         if any(n in self.scratch for n in self.current):
             return False  # scratch stores extend into the J halo of the edge chunks
@@ -334,83 +355,69 @@ class PlaneGen:
                     used.append(self.slots[name])
         return used, written
 
+    @staticmethod
+    def _lvlsync_order() -> List[str]:
+        # level-synchronous XCD-aware order: every level's work items are cut into 8 contiguous
+        # ranges, one per XCD (blocks are dispatched round-robin over the XCDs), so all XCDs
+        # stream the same few levels at a time while each keeps its neighbours in its own L2
+        return [
+            "const int per_lvl = p.n_sgroups * p.n_chunks, m8 = (per_lvl + 7) >> 3;",
+            "const int lvl = b / (m8 * 8), loc = b - lvl * m8 * 8;",
+            "const int w = (loc & 7) * m8 + (loc >> 3);",
+            "if (w >= per_lvl) return;  // padding block (whole workgroup)",
+            "sg = w % p.n_sgroups;",
+            "chunk = w / p.n_sgroups;",
+            "kk = p.k0 + lvl;",
+        ]
+
+    @staticmethod
+    def _xcd_order(o: int) -> List[str]:
+        """Work item -> (strip group, chunk, level) for the work orders 0 ... 4 (option ``order``)."""
+        L2 = ["// XCD-aware block remap: consecutive work items share an XCD (8 XCDs, round-robin dispatch)"]
+        L2 += xcd_remap("w0x")
+        if o == 3:
+            L2 = ["const int w = b;  // natural dispatch order"]
+        elif o == 2:
+            L2.append("const int w = (int)(((long long)w0x * p.perm_a) % nb);  // bijective scatter")
+        else:
+            L2.append("const int w = w0x;")
+        if o == 4:  # chunks slowest: chunk c+1 starts as chunk c ends on the same XCD (halo rows warm)
+            return L2 + ["sg = w % p.n_sgroups;", "const int rest = w / p.n_sgroups;", "kk = p.k0 + rest % p.nks;",
+                         "chunk = rest / p.nks;"]
+        if o == 1:
+            return L2 + ["kk = p.k0 + w % p.nks;", "const int rest = w / p.nks;", "sg = rest % p.n_sgroups;",
+                         "chunk = rest / p.n_sgroups;"]
+        return L2 + ["sg = w % p.n_sgroups;", "const int rest = w / p.n_sgroups;", "chunk = rest % p.n_chunks;",
+                     "kk = p.k0 + rest / p.n_chunks;"]
+
     def _render_variant(self, V: int, mirrored: Optional["PlaneGen"] = None) -> Tuple[str, dict]:
         k = self.kid
-        P = int(self.opts.get("prefetch", 4 if V <= 2 else 2))
+        P = self.o.prefetch if self.o.prefetch is not None else (4 if V <= 2 else 2)
         used_slots, written_slots = self._used_slots()
         scalars = self.st.scalar_params()
         L = []
         if V == 1:
-            L.append(f"struct K{k}Params {{")
-            for s in used_slots:
-                L += ["    " + x for x in kparam_decl(s, s.name in written_slots)]
-            for s in scalars:
-                L.append(f"    {s.dtype.ctype} s_{cname(s.name)};")
-            L.append("    int32_t ni, nj, nk, k0, nks, jc, n_strips, n_chunks, n_sgroups, perm_a, jsplit, jskip, ca, lvlsync;")
-            L.append("};")
-            L.append("")
+            L += params_struct(k, used_slots, written_slots, scalars, [
+                "int32_t ni, nj, nk, k0, nks, jc, n_strips, n_chunks, n_sgroups, perm_a, jsplit, jskip, ca, lvlsync;"])
         kname = f"k{k}_plane_v{V}"
-        mb = int(self.opts.get("min_blocks", 0))  # blocks per CU the register budget must allow
+        mb = self.o.min_blocks
         lb = f"{WAVE * PLANE_BLOCK_WAVES}, {mb}" if mb > 0 else f"{WAVE * PLANE_BLOCK_WAVES}"
         L.append(f"__global__ void __launch_bounds__({lb}) {kname}(const K{k}Params p) {{")
         B = []
         B.append("const int lane = (int)__lane_id();")
         B.append("const int wave = (int)(threadIdx.x >> 6);")
-        order = int(self.opts.get("order", PLANE_ORDER_AUTO))
         B.append("const int nb = (int)gridDim.x, b = (int)blockIdx.x;")
-
-        def lvlsync():
-            # level-synchronous XCD-aware order: every level's work items are cut into 8 contiguous
-            # ranges, one per XCD (blocks are dispatched round-robin over the XCDs), so all XCDs
-            # stream the same few levels at a time while each keeps its neighbours in its own L2
-            return [
-                "const int per_lvl = p.n_sgroups * p.n_chunks, m8 = (per_lvl + 7) >> 3;",
-                "const int lvl = b / (m8 * 8), loc = b - lvl * m8 * 8;",
-                "const int w = (loc & 7) * m8 + (loc >> 3);",
-                "if (w >= per_lvl) return;  // padding block (whole workgroup)",
-                "sg = w % p.n_sgroups;",
-                "chunk = w / p.n_sgroups;",
-                "kk = p.k0 + lvl;",
-            ]
-
-        def xcd_ranges(o):
-            L2 = [
-                "// XCD-aware block remap: consecutive work items share an XCD (8 XCDs, round-robin dispatch)",
-                "const int q = nb >> 3, r = nb & 7, xcd = b & 7, slot = b >> 3;",
-                "const int w0x = (xcd < r) ? xcd * (q + 1) + slot : r * (q + 1) + (xcd - r) * q + slot;",
-            ]
-            if o == 3:
-                L2 = ["const int w = b;  // natural dispatch order"]
-            elif o == 2:
-                L2.append("const int w = (int)(((long long)w0x * p.perm_a) % nb);  // bijective scatter")
-            else:
-                L2.append("const int w = w0x;")
-            if o == 4:  # chunks slowest: chunk c+1 starts as chunk c ends on the same XCD (halo rows warm)
-                L2 += ["sg = w % p.n_sgroups;", "const int rest = w / p.n_sgroups;", "kk = p.k0 + rest % p.nks;",
-                       "chunk = rest / p.nks;"]
-            elif o == 1:
-                L2 += ["kk = p.k0 + w % p.nks;", "const int rest = w / p.nks;", "sg = rest % p.n_sgroups;",
-                       "chunk = rest / p.n_sgroups;"]
-            else:
-                L2 += ["sg = w % p.n_sgroups;", "const int rest = w / p.n_sgroups;", "chunk = rest % p.n_chunks;",
-                       "kk = p.k0 + rest / p.n_chunks;"]
-            return L2
-
         B.append("int sg, chunk, kk;")
-        if order == 5:
-            B.append("{")
-            B += ["    " + x for x in lvlsync()]
-            B.append("}")
-        elif order == PLANE_ORDER_AUTO:
+        if self.o.order == PLANE_ORDER_AUTO:
             # chosen per launch by the host (p.lvlsync, see _render_host): uniform branch
             B.append("if (p.lvlsync) {")
-            B += ["    " + x for x in lvlsync()]
+            B += ["    " + x for x in self._lvlsync_order()]
             B.append("} else {")
-            B += ["    " + x for x in xcd_ranges(0)]
+            B += ["    " + x for x in self._xcd_order(0)]
             B.append("}")
         else:
             B.append("{")
-            B += ["    " + x for x in xcd_ranges(order)]
+            B += ["    " + x for x in (self._lvlsync_order() if self.o.order == 5 else self._xcd_order(self.o.order))]
             B.append("}")
         B.append(f"const int strip = sg * {PLANE_BLOCK_WAVES} + wave;")
         B.append("if (strip >= p.n_strips) return;")
@@ -448,7 +455,7 @@ class PlaneGen:
 
     def _bufld_ok(self, V: int) -> bool:
         """Row loads through buffer descriptors (option ``bufld``): 16- or 8-B lanes of 4/8-B types."""
-        mode = int(self.opts.get("bufld", -1))
+        mode = self.o.bufld
         if mode < 0:
             # auto: 4-byte lanes (4 cells per lane). hdiff f32 8192x1024x160: +4..+11 % on every
             # one of 24 HBM placements, bit-identical; hdiff f64 (2 cells per lane): -0.5 %
@@ -495,17 +502,82 @@ class PlaneGen:
         vmcnt(0)), i.e. the prefetched rows really stay in flight."""
         V = self.V
         c = cname(v.name)
-        kexpr = f"kk + ({v.dk})" if v.dk else "kk"
         nt = "true" if self._nt_load(v) else "false"
         t = v.dtype.ctype
         return [
             "{",
-            f"    const int64_t ro = (int64_t)gtmi::clampi({row_expr}, p.jlo_{c}, p.jhi_{c}) * p.sJ_{c} + "
-            f"(int64_t)gtmi::clampi({kexpr}, p.klo_{c}, p.khi_{c}) * p.sK_{c};",
+            "    " + self._load_ro(v, row_expr),
             f"    const __amdgpu_buffer_rsrc_t rs = gtmi::row_rsrc(p.p_{c} + ro + p.ilo_{c}, ({rcond}) ? nr_{v.c} : 0);",
             f"    {t} tmp[{V}];",
             f"    gtmi::bload<{t}, {V}, {nt}>(rs, bo_{v.c}, tmp);",
         ] + [f"    {dests[e]} = tmp[{e}];" for e in range(V)] + ["}"]
+
+    def _load_ro(self, v: Val, row_expr: str) -> str:
+        """``ro``: element offset of row ``row_expr`` at the value's level, both clamped to the field."""
+        c = cname(v.name)
+        kexpr = f"kk + ({v.dk})" if v.dk else "kk"
+        return (f"const int64_t ro = (int64_t)gtmi::clampi({row_expr}, p.jlo_{c}, p.jhi_{c}) * p.sJ_{c} + "
+                f"(int64_t)gtmi::clampi({kexpr}, p.klo_{c}, p.khi_{c}) * p.sK_{c};")
+
+    def _store_ro(self, name: str, v: Val) -> str:
+        """``ro``: element offset of the row and level the step stores ``name`` at."""
+        c = cname(name)
+        return f"const int64_t ro = (int64_t)({self._row(f't + ({v.lead})')}) * p.sJ_{c} + (int64_t)kk * p.sK_{c};"
+
+    def _emit_load(self, v: Val, row_expr: str, dests: List[str]) -> List[str]:
+        """Clamped row load on the lanes that need the value (``ln_``): one vector load where the
+        lane's whole vector lies inside the field (``vok_``), else element by element."""
+        V = self.V
+        c = cname(v.name)
+        t = v.dtype.ctype
+        nt = "true" if self._nt_load(v) else "false"
+        out = ["{", "    " + self._load_ro(v, row_expr), f"    if (ln_{v.c}) {{"]
+        if V == 1:
+            out.append(f"        {dests[0]} = gtmi::sload<{t}, {nt}>(p.p_{c} + li_{c} + ro);")
+        else:
+            out.append(f"        if (vok_{c}) {{")
+            if v.dtype.itemsize >= 4:
+                out.append(f"            {t} tmp[{V}];")
+                out.append(f"            gtmi::vload<{t}, {V}, {nt}>(p.p_{c} + pos + ro, tmp);")
+                for e in range(V):
+                    out.append(f"            {dests[e]} = tmp[{e}];")
+            else:
+                out.append(
+                    f"            const gtmi::vec<{t}, {V}> tmp = "
+                    f"*reinterpret_cast<const gtmi::vec<{t}, {V}>*>(p.p_{c} + pos + ro);"
+                )
+                for e in range(V):
+                    out.append(f"            {dests[e]} = tmp.v[{e}];")
+            out.append("        } else {")
+            for e in range(V):
+                out.append(
+                    f"            {dests[e]} = p.p_{c}[(int64_t)gtmi::clampi(pos + {e}, p.ilo_{c}, p.ihi_{c}) * "
+                    f"p.sI_{c} + ro];"
+                )
+            out.append("        }")
+        return out + ["    }", "}"]
+
+    # The three pieces every row loop shares: the J rings of the values (``depth`` rows of V
+    # registers each), the stages of one row step, and the rotation of the rings after it.
+    def _ring_vals(self, with_loads: bool) -> List[Val]:
+        return [v for v in self.vals if v.kind != "undef" and (with_loads or v.kind != "load")]
+
+    def _declare_rings(self, vals: List[Val]) -> List[str]:
+        return [f"{v.dtype.ctype} {v.c}_{a}_{e} = ({v.dtype.ctype})0;"
+                for v in vals for a in range(v.depth) for e in range(self.V)]
+
+    def _render_stages(self) -> List[str]:
+        S = []
+        for ti, code in enumerate(self.stage_code):
+            lead = self.stage_ext[ti][1][1]
+            S.append(f"{{  // stage {ti}: row t + {lead}")
+            S += ["    " + x for x in self._render_stage(ti, code, lead)]
+            S.append("}")
+        return S
+
+    def _rotate_rings(self, vals: List[Val]) -> List[str]:
+        return [f"{v.c}_{a}_{e} = {v.c}_{a - 1}_{e};"
+                for v in vals for a in range(v.depth - 1, 0, -1) for e in range(self.V)]
 
     def _render_body_slots(self, V: int, P: int) -> List[str]:
         """Row loop of an interior strip with buffer-descriptor loads and slot rings.
@@ -529,13 +601,8 @@ class PlaneGen:
         for v in loads:
             need = v.depth + max(1, P - 1)
             ring[v.vid] = U if v.depth + max(1, P) >= U else min(d for d in range(1, U + 1) if U % d == 0 and d >= need)
-        B = []
-        for v in self.vals:  # rings of computed values (moves between VALU results only)
-            if v.kind in ("undef", "load"):
-                continue
-            for a in range(v.depth):
-                for e in range(V):
-                    B.append(f"{v.dtype.ctype} {v.c}_{a}_{e} = ({v.dtype.ctype})0;")
+        computed = self._ring_vals(False)  # rings of computed values (moves between VALU results only)
+        B = self._declare_rings(computed)
         for v in loads:
             lo, hi = self._lane_range(v)
             c = cname(v.name)
@@ -572,18 +639,7 @@ class PlaneGen:
                 rcond = f"t + {pv} >= {first} && t + {pv} < jce"
                 S += self._emit_bload(v, self._row(f"t + {pv} + ({v.lead})"),
                                       [f"sl{(u + pv) % R}_{v.c}_{e}" for e in range(V)], rcond)
-            for ti, code in enumerate(self.stage_code):
-                lead = self.stage_ext[ti][1][1]
-                S.append(f"{{  // stage {ti}: row t + {lead}")
-                S += ["    " + x for x in self._render_stage(ti, code, lead)]
-                S.append("}")
-            S += self._render_stores_buf()
-            for v in self.vals:
-                if v.kind in ("undef", "load"):
-                    continue
-                for a in range(v.depth - 1, 0, -1):
-                    for e in range(V):
-                        S.append(f"{v.c}_{a}_{e} = {v.c}_{a - 1}_{e};")
+            S += self._render_stages() + self._render_stores_buf() + self._rotate_rings(computed)
             B.append(f"    {{  // slot copy {u}")
             B.append(f"        const int t = tt + {u};")
             B.append("        if (t >= jce) break;")
@@ -592,134 +648,75 @@ class PlaneGen:
         B.append("}")
         return B
 
-    def _render_body_v(self, V: int, P: int) -> List[str]:
-        B = []
-        # rings (+ per-element registers)
-        for v in self.vals:
-            if v.kind == "undef":
+    def _row_unroll(self, V: int, P: int) -> int:
+        """row_unroll=U: U copies of the row step per loop trip, each leaving the loop on its own
+        (uniform) bound check, so the ring rotations between copies become register renames.
+        Auto (-1, default): 4 when the rings and prefetch buffers hold <= 40 32-bit words per
+        lane (lap5: 32 words, +3 %; copy: neutral); kernels with more state lose occupancy
+        (hdiff f64 80 words: -2.4 % at U=6; profiles/r02za_sweep_row_unroll*.log)."""
+        if self.o.row_unroll >= 0:
+            return self.o.row_unroll
+        words = sum(v.depth * V * max(1, v.dtype.itemsize // 4) for v in self.vals if v.kind != "undef")
+        words += sum(P * V * max(1, v.dtype.itemsize // 4) for v in self.loads.values())
+        if V == 1:
+            return 0  # the 1-wide fallback stays rolled
+        if words <= 40:
+            return 4
+        # 4 cells per lane (f32): 2x (+0.7 %, +3.5 % on two boxes); 2 cells per lane
+        # (f64 hdiff): 2x/3x cost 3-4 % (profiles/r02za_sweep_row_unroll3.log)
+        return 2 if V >= 4 else 0
+
+    def _row_step(self, V: int, P: int) -> List[str]:
+        """One row step of the clamped row loop: the loaded rows move one prefetch stage on, the
+        row ``P`` steps ahead is requested, then stages, stores and ring rotation."""
+        S = []
+        for v in self.loads.values():
+            first = -(v.needed_lo + v.lead)
+            if P == 0:
+                S.append(f"if (t >= {first})")
+                S += ["    " + x for x in self._emit_load(v, self._row(f"t + ({v.lead})"),
+                                                          [f"{v.c}_0_{e}" for e in range(V)])]
                 continue
-            for a in range(v.depth):
+            for e in range(V):
+                S.append(f"{v.c}_0_{e} = pf0_{v.c}_{e};")
+            for pp in range(P - 1):
                 for e in range(V):
-                    B.append(f"{v.dtype.ctype} {v.c}_{a}_{e} = ({v.dtype.ctype})0;")
-        loads = list(self.loads.values())
-        for v in loads:
+                    S.append(f"pf{pp}_{v.c}_{e} = pf{pp + 1}_{v.c}_{e};")
+            S.append(f"if (t + {P} >= {first} && t + {P} < jce)")
+            S += ["    " + x for x in self._emit_load(v, self._row(f"t + {P} + ({v.lead})"),
+                                                      [f"pf{P - 1}_{v.c}_{e}" for e in range(V)])]
+        return S + self._render_stages() + self._render_stores() + self._rotate_rings(self._ring_vals(True))
+
+    def _render_body_v(self, V: int, P: int) -> List[str]:
+        """Row loop with clamped loads (any strip): rings, ``P`` prefetch rows per loaded value,
+        the row step once or ``row_unroll`` times per trip."""
+        B = self._declare_rings(self._ring_vals(True))
+        for v in self.loads.values():
             lo, hi = self._lane_range(v)
             B.append(f"const bool ln_{v.c} = (lane >= {lo}) && (lane <= {hi});")
             for pp in range(P):
                 for e in range(V):
                     B.append(f"{v.dtype.ctype} pf{pp}_{v.c}_{e} = ({v.dtype.ctype})0;")
-
-        def emit_load(v: Val, row_expr: str, dests: List[str]) -> List[str]:
-            c = cname(v.name)
-            kexpr = f"kk + ({v.dk})" if v.dk else "kk"
-            out = [
-                "{",
-                f"    const int64_t ro = (int64_t)gtmi::clampi({row_expr}, p.jlo_{c}, p.jhi_{c}) * p.sJ_{c} + "
-                f"(int64_t)gtmi::clampi({kexpr}, p.klo_{c}, p.khi_{c}) * p.sK_{c};",
-                f"    if (ln_{v.c}) {{",
-            ]
-            if V == 1:
-                nt = "true" if self._nt_load(v) else "false"
-                out.append(f"        {dests[0]} = gtmi::sload<{v.dtype.ctype}, {nt}>(p.p_{c} + li_{c} + ro);")
-            else:
-                t = v.dtype.ctype
-                nt = "true" if self._nt_load(v) else "false"
-                out.append(f"        if (vok_{c}) {{")
-                if v.dtype.itemsize >= 4:
-                    out.append(f"            {t} tmp[{V}];")
-                    out.append(f"            gtmi::vload<{t}, {V}, {nt}>(p.p_{c} + pos + ro, tmp);")
-                    for e in range(V):
-                        out.append(f"            {dests[e]} = tmp[{e}];")
-                else:
-                    out.append(
-                        f"            const gtmi::vec<{t}, {V}> tmp = "
-                        f"*reinterpret_cast<const gtmi::vec<{t}, {V}>*>(p.p_{c} + pos + ro);"
-                    )
-                    for e in range(V):
-                        out.append(f"            {dests[e]} = tmp.v[{e}];")
-                out.append("        } else {")
-                for e in range(V):
-                    out.append(
-                        f"            {dests[e]} = p.p_{c}[(int64_t)gtmi::clampi(pos + {e}, p.ilo_{c}, p.ihi_{c}) * "
-                        f"p.sI_{c} + ro];"
-                    )
-                out.append("        }")
-            out.append("    }")
-            out.append("}")
-            return out
-
         # initial prefetch
-        for v in loads:
+        for v in self.loads.values():
             first = -(v.needed_lo + v.lead)
             for pp in range(P):
-                rcond = f"{self.t_start + pp} >= {first} && {self.t_start + pp} < jce"
-                row = self._row(f"({self.t_start + pp}) + ({v.lead})")
-                dests = [f"pf{pp}_{v.c}_{e}" for e in range(V)]
-                B.append(f"if ({rcond})")
-                B += ["    " + x for x in emit_load(v, row, dests)]
-        # row_unroll=U: U copies of the row step per loop trip, each leaving the loop on its own
-        # (uniform) bound check, so the ring rotations between copies become register renames.
-        # Auto (-1, default): 4 when the rings and prefetch buffers hold <= 40 32-bit words per
-        # lane (lap5: 32 words, +3 %; copy: neutral); kernels with more state lose occupancy
-        # (hdiff f64 80 words: -2.4 % at U=6; profiles/r02za_sweep_row_unroll*.log).
-        row_unroll = int(self.opts.get("row_unroll", -1))
-        if row_unroll < 0:
-            words = sum(v.depth * V * max(1, v.dtype.itemsize // 4) for v in self.vals if v.kind != "undef")
-            words += sum(P * V * max(1, v.dtype.itemsize // 4) for v in loads)
-            if V == 1:
-                row_unroll = 0  # the 1-wide fallback stays rolled
-            elif words <= 40:
-                row_unroll = 4
-            else:
-                # 4 cells per lane (f32): 2x (+0.7 %, +3.5 % on two boxes); 2 cells per lane
-                # (f64 hdiff): 2x/3x cost 3-4 % (profiles/r02za_sweep_row_unroll3.log)
-                row_unroll = 2 if V >= 4 else 0
+                B.append(f"if ({self.t_start + pp} >= {first} && {self.t_start + pp} < jce)")
+                B += ["    " + x for x in self._emit_load(v, self._row(f"({self.t_start + pp}) + ({v.lead})"),
+                                                          [f"pf{pp}_{v.c}_{e}" for e in range(V)])]
+        row_unroll = self._row_unroll(V, P)
+        step = self._row_step(V, P)
         if row_unroll > 1:
             B.append(f"for (int tt = {self.t_start}; ; tt += {row_unroll}) {{")
-        else:
-            B.append(f"for (int t = {self.t_start}; t < jce; ++t) {{")
-        def step_code(u: int) -> List[str]:
-            S = []
-            for v in loads:
-                first = -(v.needed_lo + v.lead)
-                if P == 0:
-                    S.append(f"if (t >= {first})")
-                    S += ["    " + x for x in emit_load(v, self._row(f"t + ({v.lead})"),
-                                                       [f"{v.c}_0_{e}" for e in range(V)])]
-                    continue
-                rcond = f"t + {P} >= {first} && t + {P} < jce"
-                row = self._row(f"t + {P} + ({v.lead})")
-                for e in range(V):
-                    S.append(f"{v.c}_0_{e} = pf0_{v.c}_{e};")
-                for pp in range(P - 1):
-                    for e in range(V):
-                        S.append(f"pf{pp}_{v.c}_{e} = pf{pp + 1}_{v.c}_{e};")
-                dests = [f"pf{P - 1}_{v.c}_{e}" for e in range(V)]
-                S.append(f"if ({rcond})")
-                S += ["    " + x for x in emit_load(v, row, dests)]
-            for ti, code in enumerate(self.stage_code):
-                lead = self.stage_ext[ti][1][1]
-                S.append(f"{{  // stage {ti}: row t + {lead}")
-                S += ["    " + x for x in self._render_stage(ti, code, lead)]
-                S.append("}")
-            S += self._render_stores()
-            for v in self.vals:
-                if v.kind == "undef":
-                    continue
-                for a in range(v.depth - 1, 0, -1):
-                    for e in range(V):
-                        S.append(f"{v.c}_{a}_{e} = {v.c}_{a - 1}_{e};")
-            return S
-
-        if row_unroll > 1:
             for u in range(row_unroll):
                 B.append(f"    {{  // row copy {u}")
                 B.append(f"        const int t = tt + {u};")
                 B.append("        if (t >= jce) break;")
-                B += ["        " + x for x in step_code(u)]
+                B += ["        " + x for x in step]
                 B.append("    }")
         else:
-            B += ["    " + x for x in step_code(0)]
+            B.append(f"for (int t = {self.t_start}; t < jce; ++t) {{")
+            B += ["    " + x for x in step]
         B.append("}")
         return B
 
@@ -735,10 +732,9 @@ class PlaneGen:
             c = cname(name)
             isz = self.st.decl(name).dtype.itemsize
             t = v.dtype.ctype
-            row = self._row(f"t + ({v.lead})")
-            nts = "true" if self.opts.get("nt_store", 1) else "false"
+            nts = "true" if self.o.nt_store else "false"
             S.append("{")
-            S.append(f"    const int64_t ro = (int64_t)({row}) * p.sJ_{c} + (int64_t)kk * p.sK_{c};")
+            S.append("    " + self._store_ro(name, v))
             S.append(f"    const bool rv = (t + ({v.lead}) >= 0) && (t + ({v.lead}) < jce);")
             S.append(f"    const __amdgpu_buffer_rsrc_t rs = gtmi::row_rsrc(p.p_{c} + ro + p.ilo_{c}, "
                      f"rv ? (p.ihi_{c} - p.ilo_{c} + 1) * {isz} : 0);")
@@ -754,7 +750,6 @@ class PlaneGen:
             if not self._mem_backed(name):
                 continue
             c = cname(name)
-            row = self._row(f"t + ({v.lead})")
             if name in self.scratch:
                 (eilo, eihi), (ejlo, ejhi) = self.plan.scratch_extent[name]
                 rcond = (
@@ -770,8 +765,8 @@ class PlaneGen:
                 rcond = f"(t + ({v.lead}) >= 0) && (t + ({v.lead}) < jce)"
                 econd = [f"own_{e}" for e in range(V)]
             S.append(f"if ({rcond}) {{")
-            S.append(f"    const int64_t ro = (int64_t)({row}) * p.sJ_{c} + (int64_t)kk * p.sK_{c};")
-            nts = "true" if (self.opts.get("nt_store", 1) and name not in self.scratch) else "false"
+            S.append("    " + self._store_ro(name, v))
+            nts = "true" if (self.o.nt_store and name not in self.scratch) else "false"
             if V == 1:
                 S.append(
                     f"    if ({econd[0]}) gtmi::sstore<{v.dtype.ctype}, {nts}>(p.p_{c} + (int64_t)i_0 * p.sI_{c} + ro, "
@@ -805,13 +800,9 @@ class PlaneGen:
         H.append(f"    int k0 = {lo}, k1 = {hi};")
         H.append("    if (k0 < 0) k0 = 0; if (k1 > nk) k1 = nk;")
         H.append("    if (k1 > k0 && ni > 0 && nj > 0) {")
-        H.append(f"        K{k}Params p;")
-        for s in used_slots:
-            H += ["        " + x for x in host_fill(s, "p", s.name in written_slots)]
-        for i_s, s in enumerate(self.st.scalar_params()):
-            H.append(f"        memcpy(&p.s_{cname(s.name)}, &sc[{i_s}], sizeof(p.s_{cname(s.name)}));")
+        H += ["        " + x for x in host_params(k, used_slots, written_slots, self.st.scalar_params())]
         H.append("        p.ni = ni; p.nj = nj; p.nk = nk; p.k0 = k0; p.nks = k1 - k0; p.jsplit = jsplit; p.jskip = jskip;")
-        jchunk = int(self.opts.get("jchunk", 0))
+        jchunk, order = self.o.jchunk, self.o.order
         vecs = sorted(launches, reverse=True)
         H.append("        int vsel = 1;")
         for V in vecs:
@@ -844,7 +835,6 @@ class PlaneGen:
                 )
             H.append("            p.ca = (jsplit + p.jc - 1) / p.jc;  // chunks of the first row range")
             H.append("            p.n_chunks = p.ca + (nj - jsplit - jskip + p.jc - 1) / p.jc;")
-            order = int(self.opts.get("order", PLANE_ORDER_AUTO))
             if order == PLANE_ORDER_AUTO:
                 # level-synchronous order for small launches: measured faster for planes of <= 1M
                 # cells over <= 80 levels (lap5 1024^2x80 +3.5 %, copy 1024^2x80 +4.6 %), slower or
@@ -891,7 +881,7 @@ class PlaneGen:
                 if key not in shuffles:
                     nm = f"sh{len(shuffles)}"
                     shuffles[key] = nm
-                    if int(self.opts.get("dpp", 1)):  # DPP wave rotate for +-1 lanes (gtmi_device.h)
+                    if self.o.dpp:
                         out.append(f"const {ref.val.dtype.ctype} {nm} = gtmi::shfl_c<{qd}>({ref.val.c}_{slot}_{r});")
                     else:
                         out.append(f"const {ref.val.dtype.ctype} {nm} = gtmi::shfl({ref.val.c}_{slot}_{r}, {qd});")
@@ -912,11 +902,11 @@ class PlaneGen:
                 return f"{ref.val.c}_{slot}_{r}"
 
             rend = _VRenderer(resolve, lambda n: f"s_{cname(n)}", self._axis_index(lead, e))
-            rend.exact_fma = bool(int(self.opts.get("exact_fma", 1)))
+            rend.exact_fma = bool(self.o.exact_fma)
             if V > 1:
                 out.append(f"// element {e}")
             for s in code:
-                out += self._stmt(s, rend, e, lead)
+                out += render_stmt(s, rend, lambda x, e=e: self._leaf(x, rend, e), f"i_{e}", self._row(f"t + ({lead})"))
             for s in code:
                 if isinstance(s, VInit):
                     out.append(f"{s.val.c}_0_{e} = {s.val.c}_{e};")
@@ -928,7 +918,8 @@ class PlaneGen:
 
         return ax
 
-    def _stmt(self, s, rend, e, lead) -> List[str]:
+    @staticmethod
+    def _leaf(s, rend, e) -> List[str]:
         if isinstance(s, VInit):
             t = s.val.dtype.ctype
             init = rend(s.prev) if s.prev is not None else f"({t})0"
@@ -936,29 +927,6 @@ class PlaneGen:
         if isinstance(s, VAssign):
             target = f"{s.val.c}_{e}" if not s.top_level else f"{s.val.c}_0_{e}"
             return [f"{target} = {rend(s.value)};"]
-        if isinstance(s, ir.If):
-            out = [f"if ({rend(s.cond)}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, e, lead)]
-            if s.orelse:
-                out.append("} else {")
-                for x in s.orelse:
-                    out += ["    " + y for y in self._stmt(x, rend, e, lead)]
-            out.append("}")
-            return out
-        if isinstance(s, ir.While):
-            out = [f"while ({rend(s.cond)}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, e, lead)]
-            out.append("}")
-            return out
-        if isinstance(s, ir.HorizontalRegion):
-            cond = region_condition(s.masks, f"i_{e}", self._row(f"t + ({lead})"), "p.ni", "p.nj")
-            out = [f"if ({cond}) {{"]
-            for x in s.body:
-                out += ["    " + y for y in self._stmt(x, rend, e, lead)]
-            out.append("}")
-            return out
         raise TypeError(type(s))
 
 
@@ -999,6 +967,3 @@ class _VRenderer(ExprRenderer):
         if isinstance(e, VRef):
             return self.resolve(e)
         return super().r(e)
-
-
-# ------------------------------------------------------------------------------------------
