@@ -437,6 +437,8 @@ def _is_torch(obj) -> bool:
     return mod.startswith("torch")
 
 
+from gt4py_amd.storage import reduce  # noqa: E402  (storage.reduce: reductions over the compute domain)
+
 __all__ = [
     "REGISTRY",
     "register",
@@ -448,6 +450,7 @@ __all__ = [
     "from_array",
     "assign",
     "contiguous",
+    "reduce",
     "to_numpy",
     "cpu_copy",
     "normalize_storage_spec",
