@@ -46,6 +46,7 @@ from gt4py_amd.runtime import jit
 
 _SRC = os.path.join(jit.CSRC_DIR, "gtmi_reduce.hip")
 _HEADER = os.path.join(jit.INCLUDE_DIR, "gtmi_reduce.h")
+_RULES = os.path.join(jit.CSRC_DIR, "gtmi_reduce_rules.h")  # shared with gtmi_reduce_axis.hip
 _lock = threading.Lock()
 _lib = None
 
@@ -343,9 +344,11 @@ def plan(shape: Sequence[int], a_strides: Sequence[int], b_strides: Optional[Seq
 def library_path() -> str:
     with open(_SRC) as f:
         source = f.read()
-    with open(_HEADER, "rb") as f:  # not among jit's hashed headers: make it part of this key
-        digest = hashlib.sha256(f.read()).hexdigest()[:16]
-    return jit.compile_source(source, extra_flags=[f"-DGTMI_REDUCE_HEADER_DIGEST=0x{digest}"])
+    h = hashlib.sha256()
+    for path in (_HEADER, _RULES):  # not among jit's hashed headers: make them part of this key
+        with open(path, "rb") as f:
+            h.update(f.read())
+    return jit.compile_source(source, extra_flags=[f"-DGTMI_REDUCE_HEADER_DIGEST=0x{h.hexdigest()[:16]}"])
 
 
 def _library():
@@ -517,12 +520,28 @@ def _prepare(arr, b, origin, domain, stream, blocks):
     return None, _DevicePass(va, vb, dt, stream, blocks), dt
 
 
-def scan(arr, b=None, *, origin=None, domain=None, stream=None, _blocks=None):
+def _axes(arr, axis):
+    """The reduced dimensions for ``axis=``; None for the scalar path (``axis=None``, or every
+    dimension listed: a 0-d result with the same bits)."""
+    if axis is None:
+        return None
+    from gt4py_amd.storage import reduce_axis
+
+    return reduce_axis.reduced_axes(arr, axis)
+
+
+def scan(arr, b=None, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """``(absmax, min, max, n_nan, n_pinf, n_ninf, count)`` of the box's summands (the products
     with ``b``'s box when ``b`` is given), in the summand type (f64 / int64). NaNs are counted and
     otherwise left out, -0.0 orders below +0.0; where nothing is left ``absmax`` is 0 (ints:
     INT64_MIN), ``min`` +inf (INT64_MAX) and ``max`` -inf (INT64_MIN). ``count`` is a Python int;
-    for device tensors the other six are 0-d device tensors and an empty box raises."""
+    for device tensors the other six are 0-d device tensors and an empty box raises. With ``axis=``
+    the six are arrays over the kept cells and ``count`` is the reduced count of every cell."""
+    red = _axes(arr, axis)
+    if red is not None:
+        from gt4py_amd.storage import reduce_axis
+
+        return reduce_axis.scan(arr, b, red, origin, domain, stream, _parts)
     x, p, _ = _prepare(arr, b, origin, domain, stream, _blocks)
     if p is None:
         return _scan_host(x)
@@ -531,17 +550,23 @@ def scan(arr, b=None, *, origin=None, domain=None, stream=None, _blocks=None):
             p.count_slot(raw, 5), p.count)
 
 
-def fold_sums(arr, *args, origin=None, domain=None, stream=None, _blocks=None):
+def fold_sums(arr, *args, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """``fold_sums(arr[, b], M, N) -> (S0, S1, S2)``: the fold sums of the box's summands against
     the absolute maximum ``M`` and the count ``N`` of a reduction that may cover more than this
     box (a partition: the parts' fold sums add exactly). Non-finite summands count as 0; integer
-    arrays give ``(wrap-around sum, 0, 0)``. ``M`` may be a device scalar."""
+    arrays give ``(wrap-around sum, 0, 0)``. ``M`` may be a device scalar. With ``axis=`` ``M`` is an
+    array over the kept cells (host or device) and so are the three sums."""
     if len(args) == 2:
         b, (M, N) = None, args
     elif len(args) == 3:
         b, M, N = args
     else:
         raise TypeError("fold_sums(arr[, b], M, N)")
+    red = _axes(arr, axis)
+    if red is not None:
+        from gt4py_amd.storage import reduce_axis
+
+        return reduce_axis.fold_sums(arr, b, M, N, red, origin, domain, stream, _parts)
     x, p, _ = _prepare(arr, b, origin, domain, stream, _blocks)
     if p is None:
         return _fold_sums_host(x, M, int(N))
@@ -549,7 +574,12 @@ def fold_sums(arr, *args, origin=None, domain=None, stream=None, _blocks=None):
     return p.slot(raw, 0), p.slot(raw, 1), p.slot(raw, 2)
 
 
-def _sum(arr, b, origin, domain, stream, blocks):
+def _sum(arr, b, origin, domain, stream, blocks, axis=None, parts=None):
+    red = _axes(arr, axis)
+    if red is not None:
+        from gt4py_amd.storage import reduce_axis
+
+        return reduce_axis.sum_(arr, b, red, origin, domain, stream, parts)
     x, p, dt = _prepare(arr, b, origin, domain, stream, blocks)
     if p is None:
         sc = _scan_host(x)
@@ -561,31 +591,38 @@ def _sum(arr, b, origin, domain, stream, blocks):
     return p.finish(raw, p.folds(raw, p.count), p.count)
 
 
-def sum(arr, *, origin=None, domain=None, stream=None, _blocks=None):  # noqa: A001
+def sum(arr, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):  # noqa: A001
     """Sum of the box: f64 for f32 / f64 arrays (the float sum rule), int64 with wrap-around for
-    int32 / int64 arrays; 0 for an empty box."""
-    return _sum(arr, None, origin, domain, stream, _blocks)
+    int32 / int64 arrays; 0 for an empty box. ``axis`` (an int or a tuple of ints, here and in the
+    functions below) reduces those dimensions only: one result per cell of the others, each with
+    the bits of this function on the cell's sub-box (``storage/reduce_axis.py``)."""
+    return _sum(arr, None, origin, domain, stream, _blocks, axis, _parts)
 
 
-def dot(a, b, *, origin=None, domain=None, stream=None, _blocks=None):
+def dot(a, b, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """Sum of ``a[i] * b[i]`` over the same box of two arrays of equal dtype, as ``sum`` of the
     products (one f64 multiply each for f32 / f64, int64 with wrap-around for integers)."""
-    return _sum(a, b, origin, domain, stream, _blocks)
+    return _sum(a, b, origin, domain, stream, _blocks, axis, _parts)
 
 
-def norm2(a, *, origin=None, domain=None, stream=None, _blocks=None):
+def norm2(a, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """``sqrt(dot(a, a))`` in f64."""
-    d = _sum(a, a, origin, domain, stream, _blocks)
-    if isinstance(d, np.generic):
+    d = _sum(a, a, origin, domain, stream, _blocks, axis, _parts)
+    if isinstance(d, (np.generic, np.ndarray)):
         with np.errstate(all="ignore"):
-            return np.sqrt(np.float64(d))
+            return np.sqrt(np.asarray(d, dtype=np.float64))
     import torch
 
     return torch.sqrt(d.to(torch.float64))
 
 
-def count_nonfinite(arr, *, origin=None, domain=None, stream=None, _blocks=None):
+def count_nonfinite(arr, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """int64 count of NaN / +Inf / -Inf cells of the box (0 for integer arrays and empty boxes)."""
+    red = _axes(arr, axis)
+    if red is not None:
+        from gt4py_amd.storage import reduce_axis
+
+        return reduce_axis.count_nonfinite(arr, red, origin, domain, stream, _parts)
     x, p, _ = _prepare(arr, None, origin, domain, stream, _blocks)
     if p is None:
         sc = _scan_host(x)
@@ -596,7 +633,12 @@ def count_nonfinite(arr, *, origin=None, domain=None, stream=None, _blocks=None)
     return p.count_slot(p.scan(), 6)
 
 
-def _extremum(arr, which, origin, domain, stream, blocks):
+def _extremum(arr, which, origin, domain, stream, blocks, axis=None, parts=None):
+    red = _axes(arr, axis)
+    if red is not None:
+        from gt4py_amd.storage import reduce_axis
+
+        return reduce_axis.extremum(arr, which, red, origin, domain, stream, parts)
     x, p, dt = _prepare(arr, None, origin, domain, stream, blocks)
     out_dt = np.dtype(np.int64) if (which == 0 and not _floating(dt)) else dt  # absmax of ints: int64
     count = x.size if p is None else p.count
@@ -612,22 +654,29 @@ def _extremum(arr, which, origin, domain, stream, blocks):
     return p.slot(p.scan(), 8 + which).to(storage.torch_dtype(out_dt))
 
 
-def min(arr, *, origin=None, domain=None, stream=None, _blocks=None):  # noqa: A001
+def min(arr, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):  # noqa: A001
     """Minimum of the box in the array's dtype: NaN when any cell is (as ``np.min``), -0.0 below
     +0.0; ``ValueError`` for an empty box."""
-    return _extremum(arr, 1, origin, domain, stream, _blocks)
+    return _extremum(arr, 1, origin, domain, stream, _blocks, axis, _parts)
 
 
-def max(arr, *, origin=None, domain=None, stream=None, _blocks=None):  # noqa: A001
+def max(arr, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):  # noqa: A001
     """Maximum of the box, as ``min``."""
-    return _extremum(arr, 2, origin, domain, stream, _blocks)
+    return _extremum(arr, 2, origin, domain, stream, _blocks, axis, _parts)
 
 
-def absmax(arr, *, origin=None, domain=None, stream=None, _blocks=None):
+def absmax(arr, *, axis=None, origin=None, domain=None, stream=None, _blocks=None, _parts=None):
     """Maximum of ``|x|`` over the box: the array's dtype for floats (NaN when any cell is),
     int64 for integers (computed in int64); ``ValueError`` for an empty box."""
-    return _extremum(arr, 0, origin, domain, stream, _blocks)
+    return _extremum(arr, 0, origin, domain, stream, _blocks, axis, _parts)
+
+
+def plan_axis(shape, axis, a_strides, b_strides=None):
+    """``storage.reduce_axis.plan_axis``: the canonical kept and reduced groups and the path."""
+    from gt4py_amd.storage import reduce_axis
+
+    return reduce_axis.plan_axis(shape, axis, a_strides, b_strides)
 
 
 __all__ = ["count_nonfinite", "min", "max", "absmax", "sum", "dot", "norm2", "scan", "fold_sums", "fold_plan",
-           "ceil_log2", "plan", "library_path", "abi_version", "combine_scans_device"]
+           "ceil_log2", "plan", "plan_axis", "library_path", "abi_version", "combine_scans_device"]
